@@ -5,7 +5,12 @@ images/sec, 640x480, N keypoints, inference+train).
 Default workload = BASELINE config C2: ResNet-34-8s, K=4, 640x480, batch 32
 inference per GPU (train-mode BN exactly like the reference's analysis.py /
 Prediction.predict, fused K-channel head, heatmap + argmax decode) — the
-line's `value`.  The same run also times, as extra keys of the one JSON line:
+line's `value`.  A plain run sets up, warms up, times ``--steps`` steps, writes
+the last step's outputs if ``--dump-outputs DIR`` is given, and prints the line.
+``--full`` adds everything else: the roofline pass of each leg (a second pass
+with every conv launch event-timed, priced against the committed profiles) and,
+as extra keys of the one JSON line:
+  * "north_star_scaling": C2 on a 64-image batch split over the ranks;
   * "train": one training iteration per step (forward, fused fp64 BCE,
     backward, RCCL all-reduce of gradients at N>1, FusedAdam) on config C3's
     per-GPU shard (batch 8 of the 64-image global batch at N=8);
@@ -41,6 +46,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: Peak FP32 (matrix), dense
 PEAK_FP16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/FP16 MFMA ~2.5 PF dense (spec)
 PEAK_HBM_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE_BYTES = 32 << 20    # --dump-outputs: a larger array is written as a seeded sample of this size
 
 
 def parse():
@@ -67,8 +73,15 @@ def parse():
     ap.add_argument("--stage-precision", default=None, metavar="L1,L2,L3,L4",
                     help="inference with --precision f16: per-stage conv arithmetic, each of f16 / f16x3 for "
                          "layer1..layer4 (Policy.stage_precision; DESIGN 'Per-stage precision')")
-    ap.add_argument("--no-extras", action="store_true", help="main line only (no train / fp32 legs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline pass, the north_star / "
+                         "train / fp32 legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64; a heatmap batch over %d MB as a fixed seeded sample)"
+                         % (DUMP_SAMPLE_BYTES >> 20))
+    ap.add_argument("--no-extras", action="store_true", help="--full: main line only (no train / fp32 legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget for the CPU baseline sample")
     ap.add_argument("--tune", action="append", default=[], metavar="FIELD=VALUE",
                     help="A/B tooling: a non-default tuning field of hkp.policy.Policy (repeatable)")
@@ -374,10 +387,30 @@ def north_star_leg(precision, args, dev, rank, world):
     return leg
 
 
-def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard_of=None):
+def dump_array(dirname, name, t):
+    """--dump-outputs: DIR/<name>.npy, float64 as it is and everything else as float32.
+    An array over DUMP_SAMPLE_BYTES is written as its elements at fixed seeded flat
+    indices (the same indices every run), 1-D."""
+    import numpy as np
+    t = t.detach()
+    if t.dtype != torch.float64:
+        t = t.float()
+    n_max = DUMP_SAMPLE_BYTES // t.element_size()
+    if t.numel() > n_max:
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), n_max))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
+def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard_of=None, roofline=True,
+            dump_dir=None):
     """Time `steps` steps of one workload; return its metrics (rank 0 gets them).
     shard_of = (G, i): the images are slice i (batch images) of the seeded G-image
-    batch (a strong-scaling shard); default: each rank's own seeded batch."""
+    batch (a strong-scaling shard); default: each rank's own seeded batch.
+    roofline: after the timed steps, the event-timed pass the "roofline" key comes
+    from.  dump_dir: rank 0 writes what the last timed step returned there
+    (inference: heatmaps and keypoints; training: the loss, and the parameters the
+    step left), before any further step runs."""
     import hkp
     from hkp import ops, parallel
     from hkp.policy import Policy
@@ -413,7 +446,7 @@ def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard
                 hm, yx = model.heatmaps_and_keypoints(x)
                 if dist:                                   # every rank ends with all keypoints
                     parallel.gather_keypoints_fixed(yx, gathered)
-                return hm
+                return hm, yx
     else:
         from hkp import train as hkp_train
         trainer = hkp_train.Trainer(model, lr=1e-4, weight_decay=1e-4, distributed=dist, sync_bn=sync_bn)
@@ -429,8 +462,9 @@ def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    last = step() if steps > 0 else None     # only the last step's result is kept
     torch.cuda.synchronize()
     if dist:
         torch.distributed.barrier()
@@ -440,17 +474,28 @@ def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
-
-    # roofline pass: the same steps again with every conv launch event-timed
-    reps = max(3, min(steps, 10))
-    ops.set_observer(timer)          # not before: the timed steps carry no instrumentation
-    timer.on = True
-    for _ in range(reps):
-        step()
-    agg = timer.summary()
-    timer.on = False
-    ops.set_observer(None)
     peak_mem = torch.cuda.max_memory_allocated(dev) / 1e9
+    if dump_dir and rank == 0 and last is not None:
+        os.makedirs(dump_dir, exist_ok=True)
+        if mode == "infer":
+            dump_array(dump_dir, "heatmaps", last[0])
+            dump_array(dump_dir, "keypoints", last[1])
+        else:
+            dump_array(dump_dir, "loss", last)
+            dump_array(dump_dir, "parameters", torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+    del last
+
+    if roofline:
+        # roofline pass: the same steps again with every conv launch event-timed
+        reps = max(3, min(steps, 10))
+        ops.set_observer(timer)          # not before: the timed steps carry no instrumentation
+        timer.on = True
+        for _ in range(reps):
+            step()
+        agg = timer.summary()
+        timer.on = False
+        ops.set_observer(None)
+        peak_mem = torch.cuda.max_memory_allocated(dev) / 1e9
     del model, x, uv
     if mode != "infer":
         del trainer
@@ -459,6 +504,18 @@ def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard
 
     value = B * steps * world / elapsed
     fl_img = conv_flops_per_image(args.backbone, K, H, W)
+    leg = {"value": value, "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup,
+           "batch_per_gpu": B, "global_batch": B * world,
+           "model_tflops": value / world * fl_img * (3 if mode == "train" else 1) / 1e12,
+           "peak_hbm_gb": peak_mem}
+    if roofline:
+        leg["roofline"] = leg_roofline(agg, timer, reps, mode, precision, B, K, H, W, args, elapsed, steps)
+    return leg
+
+
+def leg_roofline(agg, timer, reps, mode, precision, B, K, H, W, args, elapsed, steps):
+    """The "roofline" key of a leg from its event-timed pass (`reps` steps; agg =
+    timer.summary()) and the committed profiles of the same workload."""
     # dominant kernel = the conv symbol with the most event-timed time
     dom_sym, (cnt, fl, nb, ms) = max(agg.items(), key=lambda kv: kv[1][3])
     alg = (fl / cnt) / ((ms / cnt) * 1e-3) / 1e12          # algorithmic (fp32-equivalent) TFLOP/s
@@ -530,10 +587,7 @@ def run_leg(mode, precision, batch, args, dev, rank, world, steps, warmup, shard
         roof["frac"] = roof["achieved"] / peak
         roof["frac_from_trace"] = roof["frac"]
         roof["frac_source"] = "rocprof trace (%s); frac_events: this run's HIP events" % roof["rocprof_source"]
-    return {"value": value, "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup,
-            "batch_per_gpu": B, "global_batch": B * world, "roofline": roof,
-            "model_tflops": value / world * fl_img * (3 if mode == "train" else 1) / 1e12,
-            "peak_hbm_gb": peak_mem}
+    return roof
 
 
 def main():
@@ -575,9 +629,10 @@ def main():
     else:
         batch = args.batch or (32 if args.mode == "infer" else 8)
 
-    main_leg = run_leg(args.mode, precision, batch, args, dev, rank, world, args.steps, args.warmup, shard_of=shard)
+    main_leg = run_leg(args.mode, precision, batch, args, dev, rank, world, args.steps, args.warmup, shard_of=shard,
+                       roofline=args.full, dump_dir=args.dump_outputs)
     extras = {}
-    default_c2 = (args.mode, args.backbone, args.keypoints, args.height, args.width) == \
+    default_c2 = args.full and (args.mode, args.backbone, args.keypoints, args.height, args.width) == \
         ("infer", "resnet34", 4, 480, 640)
     if not args.no_extras and default_c2 and not args.global_batch and NORTH_STAR_GLOBAL_BATCH % world == 0:
         extras["north_star_scaling"] = north_star_leg(precision, args, dev, rank, world)
@@ -618,12 +673,13 @@ def main():
             "collectives": ("gloo REHEARSAL (ranks share one GPU: not a measurement)" if rehearse
                             else "rccl" if world > 1 else "none"),
             "input": "fp32 NCHW (ToTensor)" if args.input == "f32" else "uint8 HWC BGR (ToTensor fused into the stem)"},
-        "roofline": main_leg["roofline"],
         "model_tflops": main_leg["model_tflops"],
         "peak_hbm_gb": main_leg["peak_hbm_gb"],
     }
+    if args.full:
+        out["roofline"] = main_leg["roofline"]
     out.update(extras)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     print(json.dumps(out))
     if dist:

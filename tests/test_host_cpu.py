@@ -487,3 +487,43 @@ def test_bench_names_each_config():
     # north_star's strong-scaling workload: C2 on a 64-image batch split over the ranks
     assert n("infer", "resnet34", 4, 480, 640, "f16x3", 8, 64, 8).startswith("north_star scaling: C2 batch 64 over 8")
     assert n("infer", "resnet34", 4, 480, 640, "f16", 8, 64, 8).startswith("custom strong")
+
+
+def test_bench_dump_array_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a small array is written whole (float32; float64
+    stays float64), a larger one as the elements at the same seeded indices every
+    run, within the size cap."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    yx = torch.arange(24, dtype=torch.int32).reshape(3, 4, 2)
+    bench.dump_array(str(tmp_path), "keypoints", yx)
+    got = np.load(tmp_path / "keypoints.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4, 2) and np.array_equal(got, yx.numpy())
+    bench.dump_array(str(tmp_path), "loss", torch.tensor(0.25, dtype=torch.float64))
+    assert np.load(tmp_path / "loss.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 400)
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    bench.dump_array(str(tmp_path), "a", big)
+    bench.dump_array(str(tmp_path), "b", big + 1)
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert a.shape == (100,) and a.nbytes <= 400
+    assert np.array_equal(b, a + 1)                     # the same indices both times
+    assert np.all(np.diff(a) >= 0) and 0 <= a.min() and a.max() < 1000 and len(np.unique(a)) > 50
+
+
+def test_bench_plain_run_is_the_default():
+    """What the headline figure does not need runs only behind --full."""
+    sys.path.insert(0, REPO)
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "d"
+    finally:
+        sys.argv = old

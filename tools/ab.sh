@@ -11,7 +11,7 @@ ARGS=$1; shift
 for rep in 1 2; do
   i=0
   for v in "$@"; do
-    timeout -k 10 200 python -u bench.py $ARGS $v --no-extras --no-cpu-baseline > $O/${i}_$rep.log 2>&1
+    timeout -k 10 200 python -u bench.py --full $ARGS $v --no-extras --no-cpu-baseline > $O/${i}_$rep.log 2>&1
     python3 -c "import json,sys; d=json.loads(open('$O/${i}_$rep.log').read().strip().splitlines()[-1]); print('%-40s rep $rep  %8.1f img/s  %7.3f ms  %s %.3f' % ('$v', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac']))"
     i=$((i+1))
   done

@@ -9,6 +9,6 @@ timeout -k 10 300 python -u -m pytest -x -s -v --timeout 240 --timeout-method th
 timeout -k 10 300 python -u -m pytest -x -s -v --timeout 240 --timeout-method thread tests/test_gpu_scale.py \
     -k "r50_bench_resolution" >> $out/pytest.log 2>&1 || exit $?
 for p in f16 f16x2a f16x2w f16x3; do
-    timeout -k 10 300 python bench.py --backbone resnet50 --keypoints 8 --batch 128 --precision $p --steps 10 \
+    timeout -k 10 300 python bench.py --full --backbone resnet50 --keypoints 8 --batch 128 --precision $p --steps 10 \
         --warmup 3 --no-extras --no-cpu-baseline > $out/bench_$p.log 2>&1 || exit $?
 done

@@ -26,7 +26,7 @@ profile)
     bash tools/round_profile.sh r04_v2
     timeout -k 10 300 python -u tools/bnin_ab.py > gpurun_out/r04_v2/bnin_ab.log 2>&1
     bash tools/bench_ab.sh train_a3 "--mode train" "--mode train --tune dgrad_overlap_tile=11" 2
-    timeout -k 10 600 python -u bench.py --mode train --backbone resnet50 --keypoints 8 --height 960 --width 1280 \
+    timeout -k 10 600 python -u bench.py --full --mode train --backbone resnet50 --keypoints 8 --height 960 --width 1280 \
         --batch 32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_c5.log 2>&1
     ;;
 fb)
@@ -41,7 +41,7 @@ fb_prof)
     i=0
     for cfg in "--tune fuse_input_bn_a3=1" "" "--tune x3_tile=9"; do
         i=$((i + 1))
-        timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p$i -o run -- python3 bench.py --steps 10 \
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p$i -o run -- python3 bench.py --full --steps 10 \
             --no-extras --no-cpu-baseline $cfg > $O/p$i.log 2>&1
         DB=$O/p$i/run_results.db
         [ -f $DB ] || DB=$(ls $O/p$i/*/run_results.db 2>/dev/null | head -1)
@@ -52,7 +52,7 @@ fb_prof)
 host)
     timeout -k 10 300 python -u tools/host_cost.py --mode train --steps 10 --profile > $O/train.log 2>&1
     timeout -k 10 300 python -u tools/host_cost.py --mode infer --steps 10 > $O/infer.log 2>&1
-    timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
+    timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
     ;;
 train_ab)
     timeout -k 10 500 python -u tools/train_ab.py "" "overlap_min_gflop=20" "overlap_min_gflop=60" "overlap_wgrad=0" \
@@ -81,8 +81,8 @@ c4_fuse)
     ;;
 train_check)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
-    timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --mode train --steps 10 \
+    timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full --mode train --steps 10 \
         --no-cpu-baseline > $O/prof.log 2>&1
     DB=$O/prof/run_results.db
     [ -f $DB ] || DB=$(ls $O/prof/*/run_results.db 2>/dev/null | head -1)
@@ -93,7 +93,7 @@ train_check)
 final)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-    timeout -k 10 300 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 300 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 *)
     echo "unknown subcommand $cmd" >&2

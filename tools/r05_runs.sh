@@ -58,7 +58,7 @@ case $cmd in
 check)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     echo "pytest: $(tail -1 $O/pytest_gpu.log)"
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 duo)
     timeout -k 10 400 python -u -m pytest -x -v --timeout 200 --timeout-method thread tests/test_gpu_precision.py \
@@ -72,7 +72,7 @@ duo)
     echo "infer_ab ok"
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     echo "pytest: $(tail -1 $O/pytest_gpu.log)"
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 store)
     timeout -k 10 500 python -u tools/conv_ab.py --tiles 0,13 --stores 0,2,3 --rounds 5 --iters 5 \
@@ -103,8 +103,8 @@ verify)
     echo "pytest: $(tail -1 $O/pytest_gpu.log)"
     timeout -k 10 500 python -u tools/infer_ab.py "" "f16_tile_1x1=12,f16_tile_kxk=12" \
         --backbone resnet50 --keypoints 8 --batch 128 --precision f16 --rounds 7 --iters 5 > $O/ab_c4.log 2>&1
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
-    timeout -k 10 400 python -u bench.py --backbone resnet50 --keypoints 8 --batch 128 --precision f16 \
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full --backbone resnet50 --keypoints 8 --batch 128 --precision f16 \
         --no-cpu-baseline > $O/bench_c4.log 2>&1
     ;;
 halo)
@@ -116,10 +116,10 @@ halo)
     timeout -k 10 300 python -u tools/conv_ab.py --tiles 0 --shapes layer1,c4_l1_c2,h128 --rounds 7 --iters 10 \
         > $O/conv_b.log 2>&1
     timeout -s KILL 120 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE \
-        --kernel-include-regex "halo" -d $O/pmc/pass1 -o run -- python3 bench.py --steps 3 --no-extras \
+        --kernel-include-regex "halo" -d $O/pmc/pass1 -o run -- python3 bench.py --full --steps 3 --no-extras \
         --no-cpu-baseline > $O/pmc1.log 2>&1
     timeout -s KILL 120 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE \
-        --kernel-include-regex "halo" -d $O/pmc_c4/pass1 -o run -- python3 bench.py --steps 2 --no-extras \
+        --kernel-include-regex "halo" -d $O/pmc_c4/pass1 -o run -- python3 bench.py --full --steps 2 --no-extras \
         --no-cpu-baseline --backbone resnet50 --keypoints 8 --batch 128 --precision f16 > $O/pmc2.log 2>&1
     python3 tools/pmc_summary.py $O/pmc $O/pmc_c2.json > $O/pmc_c2.txt
     python3 tools/pmc_summary.py $O/pmc_c4 $O/pmc_c4.json > $O/pmc_c4.txt
@@ -130,7 +130,7 @@ syncbn)
     timeout -k 10 600 python -u -m pytest -x -v --timeout 500 --timeout-method thread tests/test_gpu_syncbn.py \
         > $O/pytest_syncbn.log 2>&1
     echo "pytest syncbn: $(tail -1 $O/pytest_syncbn.log)"
-    timeout -k 10 600 python -u bench.py --gpus 2 --rehearse-gloo --steps 3 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 600 python -u bench.py --full --gpus 2 --rehearse-gloo --steps 3 --warmup 1 --no-cpu-baseline \
         > $O/rehearse_n2.log 2>&1
     echo "rehearsal ok"
     ;;
@@ -157,8 +157,8 @@ prio)
     ;;
 b8)
     # the north_star shard (C2 network, batch 8 on one GPU): bench line + kernel trace
-    timeout -k 10 300 python -u bench.py --batch 8 --no-extras --no-cpu-baseline > $O/bench_b8.log 2>&1
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --batch 8 --steps 10 \
+    timeout -k 10 300 python -u bench.py --full --batch 8 --no-extras --no-cpu-baseline > $O/bench_b8.log 2>&1
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full --batch 8 --steps 10 \
         --no-extras --no-cpu-baseline > $O/prof.log 2>&1
     DB=$O/prof/run_results.db
     [ -f $DB ] || DB=$(ls $O/prof/*/run_results.db 2>/dev/null | head -1)
@@ -168,9 +168,9 @@ b8)
     rm -rf $O/prof
     ;;
 c5)
-    timeout -k 10 400 python -u bench.py $C5 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_c5.log 2>&1
+    timeout -k 10 400 python -u bench.py --full $C5 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_c5.log 2>&1
     echo "bench ok"
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py $C5 --steps 3 \
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full $C5 --steps 3 \
         --warmup 2 --no-cpu-baseline > $O/prof.log 2>&1
     DB=$O/prof/run_results.db
     [ -f $DB ] || DB=$(ls $O/prof/*/run_results.db 2>/dev/null | head -1)
@@ -195,10 +195,10 @@ frac)
     timeout -k 10 500 python -u tools/train_ab.py "frac=0" "" "frac=2" --rounds 5 --iters 10 > $O/ab_train.log 2>&1
     ;;
 rehearse8)
-    timeout -k 10 500 python -u bench.py --gpus 4 --rehearse-gloo --steps 2 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 500 python -u bench.py --full --gpus 4 --rehearse-gloo --steps 2 --warmup 1 --no-cpu-baseline \
         > $O/rehearse_n4.log 2>&1
     echo "n4 ok"
-    timeout -k 10 700 python -u bench.py --gpus 8 --rehearse-gloo --steps 2 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 700 python -u bench.py --full --gpus 8 --rehearse-gloo --steps 2 --warmup 1 --no-cpu-baseline \
         > $O/rehearse_n8.log 2>&1
     echo "n8 ok"
     ;;
@@ -288,9 +288,9 @@ ups)
     timeout -k 10 400 python -u -m pytest -x -q --timeout 200 --timeout-method thread tests/test_gpu_forward.py \
         tests/test_gpu_scale.py tests/test_gpu_dropin.py > $O/pytest_ups.log 2>&1
     echo "pytest ups: $(tail -1 $O/pytest_ups.log)"
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --steps 10 --no-extras \
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full --steps 10 --no-extras \
         --no-cpu-baseline > $O/prof.log 2>&1
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof4 -o run -- python3 bench.py --steps 5 --no-extras \
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof4 -o run -- python3 bench.py --full --steps 5 --no-extras \
         --no-cpu-baseline --backbone resnet50 --keypoints 8 --batch 128 --precision f16 > $O/prof4.log 2>&1
     for L in prof prof4; do
         DB=$O/$L/run_results.db
@@ -329,7 +329,7 @@ sprio)
 final)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 *)
     echo "unknown subcommand $cmd" >&2

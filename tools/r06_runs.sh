@@ -38,7 +38,7 @@ C4="--backbone resnet50 --keypoints 8 --batch 128 --precision f16"
 # kernel trace + per-kernel stats of one bench workload: trace NAME "bench args"
 trace() {
     local name=$1 args=$2
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o run -- python3 bench.py $args \
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o run -- python3 bench.py --full $args \
         --no-extras --no-cpu-baseline > $O/prof_$name.log 2>&1
     local DB=$O/prof_$name/run_results.db
     [ -f $DB ] || DB=$(ls $O/prof_$name/*/run_results.db 2>/dev/null | head -1)
@@ -49,7 +49,7 @@ trace() {
 
 case $cmd in
 hbm)
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     echo "bench ok"
     trace c2 "--steps 5 --warmup 2"
     bash tools/pmc_passes.sh $O/pmc_c2 "--steps 2 --warmup 1 --no-extras" "."
@@ -104,10 +104,10 @@ prof)
     trace train "--mode train --steps 5 --warmup 2"
     cp $O/train_kernel_stats.csv profiles/r06_train_c3_kernel_stats_v2.csv
     echo "traces ok"
-    timeout -k 10 300 python -u bench.py > $O/bench_c2.log 2>&1
-    timeout -k 10 300 python -u bench.py --batch 8 --no-cpu-baseline --no-extras > $O/bench_b8.log 2>&1
-    timeout -k 10 300 python -u bench.py $C4 --no-cpu-baseline --no-extras > $O/bench_c4.log 2>&1
-    timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline --no-extras > $O/bench_train.log 2>&1
+    timeout -k 10 300 python -u bench.py --full > $O/bench_c2.log 2>&1
+    timeout -k 10 300 python -u bench.py --full --batch 8 --no-cpu-baseline --no-extras > $O/bench_b8.log 2>&1
+    timeout -k 10 300 python -u bench.py --full $C4 --no-cpu-baseline --no-extras > $O/bench_c4.log 2>&1
+    timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline --no-extras > $O/bench_train.log 2>&1
     ;;
 pmc)
     # PMC passes of the final tree for C4 and the C3 training shard (the C2 passes are
@@ -163,9 +163,9 @@ bnr)
         -k "backward or bwd or train or syncbn or c3 or grad" > $O/pytest_bwd.log 2>&1
     echo "pytest: $(tail -1 $O/pytest_bwd.log)"
     for i in 1 2; do
-        timeout -k 10 300 python -u bench.py --mode train --no-extras --no-cpu-baseline \
+        timeout -k 10 300 python -u bench.py --full --mode train --no-extras --no-cpu-baseline \
             --lib tools/ab_lib/libhulkkp_base.so > $O/bench_base_$i.log 2>&1
-        timeout -k 10 300 python -u bench.py --mode train --no-extras --no-cpu-baseline > $O/bench_new_$i.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --mode train --no-extras --no-cpu-baseline > $O/bench_new_$i.log 2>&1
     done
     ;;
 bnrt)
@@ -207,8 +207,8 @@ trainab)
         -k "backward or bwd or train or c3 or grad or dgrad" > $O/pytest_bwd.log 2>&1
     echo "pytest: $(tail -1 $O/pytest_bwd.log)"
     for i in 1 2 3 4; do
-        timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline --no-extras > $O/train_new_$i.log 2>&1
-        timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline --no-extras \
+        timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline --no-extras > $O/train_new_$i.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline --no-extras \
             --lib tools/ab_lib/libhulkkp_base.so > $O/train_base_$i.log 2>&1
     done
     for f in $O/train_new_*.log $O/train_base_*.log; do
@@ -225,7 +225,7 @@ proftrain)
     cp $O/pmc_train/pmc_summary.txt profiles/r06_train_c3_pmc_v3.txt
     python3 tools/hbm_table.py $O/train_kernel_stats.csv $O/pmc_train/pmc_summary.json --steps 7 --top 40 \
         > $O/train_hbm_table.txt
-    timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline --no-extras > $O/bench_train.log 2>&1
+    timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline --no-extras > $O/bench_train.log 2>&1
     ;;
 wgh2)
     # a halo wgrad build against the previous one (tools/ab_lib/libhulkkp_base.so):
@@ -240,8 +240,8 @@ wgh2)
     done
     grep -h wgrad $O/wg_new_*.log $O/wg_base_*.log
     for i in 1 2 3; do
-        timeout -k 10 300 python -u bench.py --mode train --no-extras --no-cpu-baseline > $O/train_new_$i.log 2>&1
-        timeout -k 10 300 python -u bench.py --mode train --no-extras --no-cpu-baseline \
+        timeout -k 10 300 python -u bench.py --full --mode train --no-extras --no-cpu-baseline > $O/train_new_$i.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --mode train --no-extras --no-cpu-baseline \
             --lib tools/ab_lib/libhulkkp_base.so > $O/train_base_$i.log 2>&1
     done
     for f in $O/train_new_*.log $O/train_base_*.log; do
@@ -259,12 +259,12 @@ wghpmc)
 check)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     echo "pytest: $(tail -1 $O/pytest_gpu.log)"
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 final)
     timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-    timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1
+    timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1
     ;;
 *)
     echo "unknown subcommand $cmd" >&2

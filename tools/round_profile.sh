@@ -13,22 +13,22 @@ export TMPDIR=/tmp
 mkdir -p $O
 C4="--backbone resnet50 --keypoints 8 --batch 128 --precision f16"
 if [ "${2:-}" = "pmc" ]; then
-    bash tools/pmc_passes.sh $O/pmc_infer "--steps 5 --no-extras" "conv_x3"
-    bash tools/pmc_passes.sh $O/pmc_train "--mode train --steps 5" "conv_x3|wgrad_x3"
-    bash tools/pmc_passes.sh $O/pmc_c4 "$C4 --steps 3 --no-extras" "conv_x3"
+    bash tools/pmc_passes.sh $O/pmc_infer "--full --steps 5 --no-extras" "conv_x3"
+    bash tools/pmc_passes.sh $O/pmc_train "--full --mode train --steps 5" "conv_x3|wgrad_x3"
+    bash tools/pmc_passes.sh $O/pmc_c4 "--full $C4 --steps 3 --no-extras" "conv_x3"
     echo "pmc ok"
     exit 0
 fi
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1
 echo "pytest ok: $(tail -1 $O/pytest_gpu.log)"
-timeout -k 10 300 python -u bench.py > $O/bench_infer.log 2>&1
-timeout -k 10 300 python -u bench.py --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
-timeout -k 10 300 python -u bench.py $C4 --no-cpu-baseline > $O/bench_c4.log 2>&1
+timeout -k 10 300 python -u bench.py --full > $O/bench_infer.log 2>&1
+timeout -k 10 300 python -u bench.py --full --mode train --no-cpu-baseline > $O/bench_train.log 2>&1
+timeout -k 10 300 python -u bench.py --full $C4 --no-cpu-baseline > $O/bench_c4.log 2>&1
 timeout -k 10 400 python -u tools/datapath_bench.py --n 1024 --workers 0,8,15 --decode host,device > $O/datapath.log 2>&1
 echo "bench ok"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_infer -o run -- python3 bench.py --steps 10 --no-extras --no-cpu-baseline > $O/prof_infer.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_train -o run -- python3 bench.py --mode train --steps 10 --no-cpu-baseline > $O/prof_train.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run -- python3 bench.py $C4 --steps 5 --no-extras --no-cpu-baseline > $O/prof_c4.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_infer -o run -- python3 bench.py --full --steps 10 --no-extras --no-cpu-baseline > $O/prof_infer.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_train -o run -- python3 bench.py --full --mode train --steps 10 --no-cpu-baseline > $O/prof_train.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run -- python3 bench.py --full $C4 --steps 5 --no-extras --no-cpu-baseline > $O/prof_c4.log 2>&1
 echo "kernel trace ok"
 # per-kernel stats CSV + top list + step timeline of each trace (the files profiles/ keeps)
 for L in infer train c4; do
