@@ -23,6 +23,39 @@ __device__ __forceinline__ void bn_rank_stats_store(int c, int C, long count, do
     if (c == 0) stats[2 * C] = (double)count;
 }
 
+// A segmented tile list (a mixed-height conv launch's partials: 128-, 96- and 80-row
+// tiles, hkp_conv_x3_stat_layout): up to three runs of tiles of one height, every
+// run but the last whole full tiles; by value in the kernel arguments.  SEG = false
+// (one tile height) is the form every other list takes: the table is not read.
+struct FinSegs {
+    int n = 1;                         // segments
+    int rows[3] = {0, 0, 0};           // rows per full tile
+    long t0[3] = {0, 0, 0};            // first tile
+    long r0[3] = {0, 0, 0};            // first row
+    long tiles = 0;
+};
+// rows of tile t; full: the rows of a full tile of its segment
+template <bool SEG>
+__device__ __forceinline__ long fin_tile_rows(long t, int tile_rows, long count, const FinSegs& g, int& full) {
+    if constexpr (!SEG) {
+        full = tile_rows;
+        return min((long)tile_rows, count - t * tile_rows);
+    } else {
+        const bool s2 = g.n > 2 && t >= g.t0[2], s1 = g.n > 1 && t >= g.t0[1];
+        full = s2 ? g.rows[2] : s1 ? g.rows[1] : g.rows[0];
+        const long tb = s2 ? g.t0[2] : s1 ? g.t0[1] : 0, rb = s2 ? g.r0[2] : s1 ? g.r0[1] : 0;
+        return min((long)full, count - (rb + (t - tb) * full));
+    }
+}
+// first row of tile t of a segmented list (t >= tiles: count)
+__device__ __forceinline__ long fin_seg_row0(long t, long count, const FinSegs& g) {
+    if (t >= g.tiles) return count;
+    const bool s2 = g.n > 2 && t >= g.t0[2], s1 = g.n > 1 && t >= g.t0[1];
+    const long full = s2 ? g.rows[2] : s1 ? g.rows[1] : g.rows[0];
+    const long tb = s2 ? g.t0[2] : s1 ? g.t0[1] : 0, rb = s2 ? g.r0[2] : s1 ? g.r0[1] : 0;
+    return rb + (t - tb) * full;
+}
+
 // CPB channels per block (partials_cpb); deterministic fixed-order fp64 merge
 // NT threads per block: 256, or 1024 for long tile lists (the stem's 19,200
 // tiles at C2: per-thread load chains of 75 tiles took 75 us with 256 threads).
@@ -33,12 +66,12 @@ __device__ __forceinline__ void bn_rank_stats_store(int c, int C, long count, do
 // kept in registers for the second pass — the same sums in the same order (so the
 // same bits) with one exposed load latency instead of 2 x ceil(tiles / (8 TL));
 // tile means of full tiles (tile_rows a power of two) by an exact multiply
-template <int CPB, int NT = 256, int NB = 0>
+template <int CPB, int NT = 256, int NB = 0, bool SEG = false>
 __global__ __launch_bounds__(NT) void bn_finalize_kernel(int C, long count, long tiles, int tile_rows,
                                                          const float* __restrict__ part, const float* gamma,
                                                          const float* beta, float momentum, float eps, float* rmean,
                                                          float* rvar, int64_t* nbt, float* ss, float* mi,
-                                                         double* stats) {
+                                                         double* stats, FinSegs sg) {
     constexpr int TL = NT / CPB, NW = NT / 64;
     __shared__ double red[NW][8];
     const int cl = threadIdx.x % CPB, tl = threadIdx.x / CPB, c = blockIdx.x * CPB + cl;
@@ -54,15 +87,19 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(int C, long count, long
 #pragma unroll
         for (int j = 0; j < NB; ++j) s += (double)v[j].x;
         const double mean = lanes_sum_d<CPB, NW>(s, red) / (double)count;
-        const bool pow2 = (tile_rows & (tile_rows - 1)) == 0;
-        const double inv_rows = 1.0 / (double)tile_rows;   // exact for a power of two
+        // (a segmented list: the segment of 128-row tiles takes the exact multiply)
+        const int rows0 = SEG ? sg.rows[0] : tile_rows;
+        const bool pow2 = (rows0 & (rows0 - 1)) == 0;
+        const double inv_rows = 1.0 / (double)rows0;       // exact for a power of two
         double q = 0.0;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const long t = tl + (long)j * TL;
             if (ok && t < tiles) {
-                const long n_t = min((long)tile_rows, count - t * tile_rows);
-                const double tm = pow2 && n_t == tile_rows ? (double)v[j].x * inv_rows : (double)v[j].x / (double)n_t;
+                int full;
+                const long n_t = fin_tile_rows<SEG>(t, tile_rows, count, sg, full);
+                const bool fast = pow2 && n_t == rows0 && (!SEG || sg.n == 1 || t < sg.t0[1]);
+                const double tm = fast ? (double)v[j].x * inv_rows : (double)v[j].x / (double)n_t;
                 const double dm = tm - mean;
                 q += (double)v[j].y + (double)n_t * dm * dm;
             }
@@ -102,7 +139,8 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(int C, long count, long
             for (int j = 0; j < 8; ++j) {
                 const long t = t0 + (long)j * TL;
                 if (t < tiles) {
-                    const long n_t = min((long)tile_rows, count - t * tile_rows);
+                    int full;
+                    const long n_t = fin_tile_rows<SEG>(t, tile_rows, count, sg, full);
                     const double dm = (double)v[j].x / (double)n_t - mean;
                     q += (double)v[j].y + (double)n_t * dm * dm;
                 }
@@ -142,8 +180,10 @@ __device__ __forceinline__ double fin_col_sum(double v, double (*red)[64], int t
     return a[0];
 }
 
+template <bool SEG = false>
 __global__ __launch_bounds__(1024) void bn_fin_chunk_kernel(int C, long count, long tiles, int tile_rows,
-                                                            const float* __restrict__ part, double2* __restrict__ ws) {
+                                                            const float* __restrict__ part, double2* __restrict__ ws,
+                                                            FinSegs sg) {
     __shared__ double red[FIN_TL][64];
     const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
     const bool ok = c < C;
@@ -159,14 +199,16 @@ __global__ __launch_bounds__(1024) void bn_fin_chunk_kernel(int C, long count, l
     for (int j = 0; j < FIN_TPL; ++j) s += (double)v[j].x;
     const double S = fin_col_sum(s, red, tl, cl);
     const long te = min(tiles, t0 + FIN_CHUNK);
-    const long nk = min(count, te * (long)tile_rows) - t0 * (long)tile_rows;   // rows in this chunk
+    const long nk = SEG ? fin_seg_row0(te, count, sg) - fin_seg_row0(t0, count, sg)
+                        : min(count, te * (long)tile_rows) - t0 * (long)tile_rows;   // rows in this chunk
     const double mk = S / (double)nk;
     double q = 0.0;
 #pragma unroll
     for (int j = 0; j < FIN_TPL; ++j) {
         const long t = t0 + tl + (long)FIN_TL * j;
         if (t < tiles) {
-            const long n_t = min((long)tile_rows, count - t * tile_rows);
+            int full;
+            const long n_t = fin_tile_rows<SEG>(t, tile_rows, count, sg, full);
             const double dm = (double)v[j].x / (double)n_t - mk;
             q += (double)v[j].y + (double)n_t * dm * dm;
         }
@@ -175,11 +217,12 @@ __global__ __launch_bounds__(1024) void bn_fin_chunk_kernel(int C, long count, l
     if (tl == 0 && ok) ws[blockIdx.y * (long)C + c] = make_double2(S, Q);
 }
 
+template <bool SEG = false>
 __global__ __launch_bounds__(1024) void bn_fin_merge_kernel(int C, long count, long chunks, int tile_rows,
                                                             const double2* __restrict__ ws, const float* gamma,
                                                             const float* beta, float momentum, float eps,
                                                             float* rmean, float* rvar, int64_t* nbt, float* ss,
-                                                            float* mi, double* stats) {
+                                                            float* mi, double* stats, FinSegs sg) {
     __shared__ double red[FIN_TL][64];
     const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
     const bool ok = c < C;
@@ -192,7 +235,8 @@ __global__ __launch_bounds__(1024) void bn_fin_merge_kernel(int C, long count, l
     if (ok)
         for (long k = tl; k < chunks; k += FIN_TL) {
             const double2 w = ws[k * C + c];
-            const long nk = min(rows, count - k * rows);
+            const long nk = SEG ? fin_seg_row0((k + 1) * FIN_CHUNK, count, sg) - fin_seg_row0(k * FIN_CHUNK, count, sg)
+                                : min(rows, count - k * rows);
             const double dm = w.x / (double)nk - mean;
             q += w.y + (double)nk * dm * dm;
         }
@@ -469,19 +513,23 @@ int hkp_fin_regs() { return g_fin_regs; }
 static int fin_one(const char* who, int32_t c, int64_t count, int64_t tiles, int32_t tile_rows, const float* partials,
                    const float* gamma, const float* beta, float momentum, float eps, float* running_mean,
                    float* running_var, int64_t* num_batches_tracked, float* scale_shift, float* mean_invstd,
-                   double* stats, hkp_stream_t stream) {
+                   double* stats, hkp_stream_t stream, const FinSegs* segs = nullptr) {
     HKP_CHECK_ARG(c > 0 && count > 0 && tiles > 0 && tile_rows > 0, "%s: bad sizes", who);
     HKP_CHECK_ARG(partials && (scale_shift || stats), "%s: null tensor", who);
     HKP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "%s: running stats pair", who);
-    HKP_CHECK_ARG((tiles - 1) * (int64_t)tile_rows < count && tiles * (int64_t)tile_rows >= count,
+    HKP_CHECK_ARG(segs || ((tiles - 1) * (int64_t)tile_rows < count && tiles * (int64_t)tile_rows >= count),
                   "%s: tiles/tile_rows inconsistent with count", who);
+    const FinSegs sg = segs ? *segs : FinSegs{};
     const int cpb = partials_cpb(c);
     // partials per tile lane of the 256-thread form: held in registers up to 32
     const long per = g_fin_regs ? (tiles + 256 / cpb - 1) / (256 / cpb) : 1L << 40;
-#define HKP_FIN1(CPB, NT, NB)                                                                                      \
-    hipLaunchKernelGGL((bn_finalize_kernel<CPB, NT, NB>), dim3((c + CPB - 1) / CPB), dim3(NT), 0, as_stream(stream), \
-                       c, (long)count, (long)tiles, tile_rows, partials, gamma, beta, momentum, eps, running_mean,   \
-                       running_var, num_batches_tracked, scale_shift, mean_invstd, stats)
+#define HKP_FIN2(CPB, NT, NB, SEG)                                                                                \
+    hipLaunchKernelGGL((bn_finalize_kernel<CPB, NT, NB, SEG>), dim3((c + CPB - 1) / CPB), dim3(NT), 0,             \
+                       as_stream(stream), c, (long)count, (long)tiles, tile_rows, partials, gamma, beta, momentum, \
+                       eps, running_mean, running_var, num_batches_tracked, scale_shift, mean_invstd, stats, sg)
+#define HKP_FIN1(CPB, NT, NB)                    \
+    if (segs) { HKP_FIN2(CPB, NT, NB, true); } \
+    else { HKP_FIN2(CPB, NT, NB, false); }
 #define HKP_FIN(CPB)                                  \
     if (tiles >= 4096) { HKP_FIN1(CPB, 1024, 0); } \
     else if (per <= 8) { HKP_FIN1(CPB, 256, 8); } \
@@ -494,6 +542,7 @@ static int fin_one(const char* who, int32_t c, int64_t count, int64_t tiles, int
     else { HKP_FIN(1); }
 #undef HKP_FIN
 #undef HKP_FIN1
+#undef HKP_FIN2
     HKP_LAUNCH_CHECK(who);
     return HKP_OK;
 }
@@ -506,24 +555,61 @@ extern "C" int64_t hkp_bn_finalize_workspace_bytes(int32_t c, int64_t tiles) {
 static int fin_two(const char* who, int32_t c, int64_t count, int64_t tiles, int32_t tile_rows, const float* partials,
                    const float* gamma, const float* beta, float momentum, float eps, float* running_mean,
                    float* running_var, int64_t* num_batches_tracked, float* scale_shift, float* mean_invstd,
-                   double* stats, void* workspace, int64_t ws_bytes, hkp_stream_t stream) {
+                   double* stats, void* workspace, int64_t ws_bytes, hkp_stream_t stream,
+                   const FinSegs* segs = nullptr) {
     HKP_CHECK_ARG(c > 0 && count > 0 && tiles > 0 && tile_rows > 0, "%s: bad sizes", who);
     HKP_CHECK_ARG(partials && (scale_shift || stats) && workspace, "%s: null tensor", who);
     HKP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "%s: running stats pair", who);
-    HKP_CHECK_ARG((tiles - 1) * (int64_t)tile_rows < count && tiles * (int64_t)tile_rows >= count,
+    HKP_CHECK_ARG(segs || ((tiles - 1) * (int64_t)tile_rows < count && tiles * (int64_t)tile_rows >= count),
                   "%s: tiles/tile_rows inconsistent with count", who);
+    const FinSegs sg = segs ? *segs : FinSegs{};
     const int64_t need = hkp_bn_finalize_workspace_bytes(c, tiles);
     HKP_CHECK_ARG(ws_bytes >= need, "%s: workspace %ld < %ld", who, (long)ws_bytes, (long)need);
     const long chunks = (tiles + FIN_CHUNK - 1) / FIN_CHUNK;
     hipStream_t st = as_stream(stream);
     const unsigned cg = (unsigned)((c + 63) / 64);
-    hipLaunchKernelGGL(bn_fin_chunk_kernel, dim3(cg, (unsigned)chunks), dim3(1024), 0, st, c, (long)count,
-                       (long)tiles, tile_rows, partials, (double2*)workspace);
+    if (segs)
+        hipLaunchKernelGGL(bn_fin_chunk_kernel<true>, dim3(cg, (unsigned)chunks), dim3(1024), 0, st, c, (long)count,
+                           (long)tiles, tile_rows, partials, (double2*)workspace, sg);
+    else
+        hipLaunchKernelGGL(bn_fin_chunk_kernel<false>, dim3(cg, (unsigned)chunks), dim3(1024), 0, st, c, (long)count,
+                           (long)tiles, tile_rows, partials, (double2*)workspace, sg);
     HKP_LAUNCH_CHECK(who);
-    hipLaunchKernelGGL(bn_fin_merge_kernel, dim3(cg), dim3(1024), 0, st, c, (long)count, chunks, tile_rows,
-                       (const double2*)workspace, gamma, beta, momentum, eps, running_mean, running_var,
-                       num_batches_tracked, scale_shift, mean_invstd, stats);
+    if (segs)
+        hipLaunchKernelGGL(bn_fin_merge_kernel<true>, dim3(cg), dim3(1024), 0, st, c, (long)count, chunks, tile_rows,
+                           (const double2*)workspace, gamma, beta, momentum, eps, running_mean, running_var,
+                           num_batches_tracked, scale_shift, mean_invstd, stats, sg);
+    else
+        hipLaunchKernelGGL(bn_fin_merge_kernel<false>, dim3(cg), dim3(1024), 0, st, c, (long)count, chunks, tile_rows,
+                           (const double2*)workspace, gamma, beta, momentum, eps, running_mean, running_var,
+                           num_batches_tracked, scale_shift, mean_invstd, stats, sg);
     HKP_LAUNCH_CHECK(who);
+    return HKP_OK;
+}
+
+// the host's check of a segment table (hulkkp.h: rows, tiles pairs) -> FinSegs; one
+// segment: the caller takes the unsegmented kernels
+static int fin_segs(const char* who, int64_t count, int32_t nseg, const int32_t* segments, FinSegs* sg, int64_t* tiles) {
+    HKP_CHECK_ARG(segments && nseg >= 1 && nseg <= 3 && count > 0, "%s: 1 to 3 segments", who);
+    int64_t row = 0, t = 0;
+    sg->n = nseg;
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t rows = segments[2 * i], nt = segments[2 * i + 1];
+        HKP_CHECK_ARG(rows > 0 && nt > 0, "%s: segment %d: bad rows/tiles", who, i);
+        sg->rows[i] = (int)rows;
+        sg->t0[i] = t;
+        sg->r0[i] = row;
+        if (i + 1 < nseg) {
+            row += rows * nt;              // whole full tiles
+            HKP_CHECK_ARG(row < count, "%s: segment %d reaches past count", who, i);
+        } else {
+            HKP_CHECK_ARG(row + (nt - 1) * rows < count && row + nt * rows >= count,
+                          "%s: segments inconsistent with count", who);
+        }
+        t += nt;
+    }
+    sg->tiles = t;
+    *tiles = t;
     return HKP_OK;
 }
 
@@ -555,6 +641,40 @@ extern "C" int hkp_bn_stats(int32_t c, int64_t count, int64_t tiles, int32_t til
                        nullptr, nullptr, nullptr, nullptr, stats, workspace, ws_bytes, stream);
     return fin_one("hkp_bn_stats", c, count, tiles, tile_rows, partials, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr,
                    nullptr, nullptr, nullptr, stats, stream);
+}
+
+extern "C" int hkp_bn_finalize_seg(int32_t c, int64_t count, int32_t nseg, const int32_t* segments,
+                                   const float* partials, const float* gamma, const float* beta, float momentum,
+                                   float eps, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                   float* scale_shift, float* mean_invstd, void* workspace, int64_t ws_bytes,
+                                   hkp_stream_t stream) {
+    HKP_CHECK_ARG(scale_shift, "hkp_bn_finalize_seg: null tensor");
+    FinSegs sg;
+    int64_t tiles = 0;
+    const int rc = fin_segs("hkp_bn_finalize_seg", count, nseg, segments, &sg, &tiles);
+    if (rc) return rc;
+    const FinSegs* ps = nseg > 1 ? &sg : nullptr;      // one segment: the unsegmented kernels
+    if (workspace)
+        return fin_two("hkp_bn_finalize_seg", c, count, tiles, sg.rows[0], partials, gamma, beta, momentum, eps,
+                       running_mean, running_var, num_batches_tracked, scale_shift, mean_invstd, nullptr, workspace,
+                       ws_bytes, stream, ps);
+    return fin_one("hkp_bn_finalize_seg", c, count, tiles, sg.rows[0], partials, gamma, beta, momentum, eps,
+                   running_mean, running_var, num_batches_tracked, scale_shift, mean_invstd, nullptr, stream, ps);
+}
+
+extern "C" int hkp_bn_stats_seg(int32_t c, int64_t count, int32_t nseg, const int32_t* segments, const float* partials,
+                                double* stats, void* workspace, int64_t ws_bytes, hkp_stream_t stream) {
+    HKP_CHECK_ARG(stats, "hkp_bn_stats_seg: null tensor");
+    FinSegs sg;
+    int64_t tiles = 0;
+    const int rc = fin_segs("hkp_bn_stats_seg", count, nseg, segments, &sg, &tiles);
+    if (rc) return rc;
+    const FinSegs* ps = nseg > 1 ? &sg : nullptr;
+    if (workspace)
+        return fin_two("hkp_bn_stats_seg", c, count, tiles, sg.rows[0], partials, nullptr, nullptr, 0.f, 0.f, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, stats, workspace, ws_bytes, stream, ps);
+    return fin_one("hkp_bn_stats_seg", c, count, tiles, sg.rows[0], partials, nullptr, nullptr, 0.f, 0.f, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, stats, stream, ps);
 }
 
 extern "C" int hkp_bn_finalize_ranks(int32_t c, int32_t nranks, const double* stats, const float* gamma,

@@ -90,6 +90,14 @@ struct X3Args {
     // block from per-segment fp32 slabs (sk_ws) — sk_cnt[tile] arrival counters,
     // zero on entry and left zero
     int mt0 = 0;           // m-tile offset of this launch (the split-K tail launch of conv_x3_tail_kernel)
+    // region base (a region of conv_x3_a3_mix_kernel; 0 everywhere else): the tiles'
+    // rows start at m_base — tile mt is rows m_base + (mt + mt0) * BM — and their BN
+    // partial tiles at part_base
+    int m_base = 0, part_base = 0;
+    // mixed-height launch (conv_x3_a3_mix_kernel): blocks [0, mix_b1) are the 256-row
+    // region's tiles, [mix_b1, mix_b2) the 192-row region's (from row mix_m1, partial
+    // tile mix_p1), the rest the 160-row region's (mix_m2, mix_p2); a region may be empty
+    int mix_b1 = 0, mix_b2 = 0, mix_m1 = 0, mix_m2 = 0, mix_p1 = 0, mix_p2 = 0;
     long sk_units = 0;
     float* sk_ws = nullptr;
     unsigned* sk_cnt = nullptr;
@@ -419,7 +427,7 @@ __device__ __forceinline__ void x3_bn_partials(const X3Args& a, char* smem, int 
         for (int j = 0; j < NJ; ++j) red[wm * BN + wn * NJ * CW + j * CW + lane] = colsum[j];
     }
     __syncthreads();
-    const long tile128 = (long)(m0 >> 7);
+    const long tile128 = (long)a.part_base + ((m0 - a.m_base) >> 7);
     for (int e = tid; e < 2 * BN; e += 512) {
         const int h = e / BN, c = e - h * BN;
         const int cnt = min(128, a.M - (m0 + 128 * h));
@@ -547,7 +555,7 @@ __device__ __forceinline__ void x3_bn_partials_w(const X3Args& a, float* red, in
                 }
                 x3_chan_merge(S[0], Q[0], S[1], Q[1], 1.f / (16 * NI), 8.f * NI);   // even wave, odd wave
                 const float sc = wide[32 * BN + c];
-                const long tile128 = (long)(m0 / (2 * WROWS)) + h;
+                const long tile128 = (long)a.part_base + (m0 - a.m_base) / (2 * WROWS) + h;
                 a.part[(tile128 * a.K + n0 + c) * 2 + 0] = S[0] * sc;
                 a.part[(tile128 * a.K + n0 + c) * 2 + 1] = Q[0] * (sc * sc);
             }
@@ -621,7 +629,7 @@ __device__ __forceinline__ void x3_bn_partials_w(const X3Args& a, float* red, in
     }
     if constexpr (WMP == 2) {              // 2 waves in M (160-row tiles): a wave IS a partial tile
         if (nw == 0 || lane >= CW) return;
-        const long pt = (long)(m0 / WROWS) + wm;
+        const long pt = (long)a.part_base + (m0 - a.m_base) / WROWS + wm;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = wn * NJ * CW + j * CW + lane;
@@ -642,7 +650,7 @@ __device__ __forceinline__ void x3_bn_partials_w(const X3Args& a, float* red, in
     lds_sync();
     const int nb = min(WROWS, max(0, a.M - (m0 + WROWS * (wm | 1))));   // valid rows of the odd wave of the half
     if ((wm & 1) || nw == 0 || lane >= CW) return;
-    const long tile128 = (long)(m0 / (2 * WROWS)) + (wm >> 1);
+    const long tile128 = (long)a.part_base + (m0 - a.m_base) / (2 * WROWS) + (wm >> 1);
     const float ia = 1.f / (float)nw, ib = nb > 0 ? 1.f / (float)nb : 0.f;
     const float f = (float)nw * (float)nb / (float)(nw + nb);
 #pragma unroll
@@ -1174,7 +1182,7 @@ __device__ __forceinline__ void conv_x3_tile(const X3Args& a, char* smem, int ti
     static_assert(!A_SINK || A3, "the A sink is the A3 body's");
 
     const int mt = tile / a.n_tiles, nt = tile - mt * a.n_tiles;
-    const int m0 = (mt + a.mt0) * BM, n0 = nt * BN;
+    const int m0 = a.m_base + (mt + a.mt0) * BM, n0 = nt * BN;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w / WN, wn = w % WN;
@@ -1595,6 +1603,41 @@ __global__ __launch_bounds__(512, 1) void conv_x3_a3_160x128_kernel(X3Args a) {
     __shared__ __attribute__((aligned(1024))) char smem[x3_a3_lds(160, 128)];
     x3_stamp(a, 0);
     conv_x3_tile<128, false, false, 16, P, true, 160>(a, smem, xcd_remap(blockIdx.x, gridDim.x), 0, a.nks, false);
+}
+
+// Mixed tile heights in one launch (HKP_TILE_MIX_A3, packed operands, Cout % 256
+// == 0, more than one round of tiles): a 256-row grid charges its last, partly
+// filled round as a whole one.  The three A3 bodies give the same bits per output
+// element and cost the same per row, so every CU gets 256-row tiles first and one
+// shorter tile last (x3_mix_plan: C2 layer3, 600 row-units per CU, runs 256 + 192 +
+// 160 = 38 sixteen-row blocks per CU instead of 2 rounds + a split-K tail; layer4
+// 4 x 256 + 192 = 76 instead of 5 x 256 = 80) — no slab, no combine, no workspace.
+// The block index picks the region (block-uniform); tall tiles first, since blocks
+// are dispatched in index order as CUs free up.  Every region but the last is whole
+// full tiles; only the last region's last tile is cut by M.  The XCD remap runs
+// inside each region, as in the in-launch tail of conv_x3_a3_kernel.
+template <int P>
+__global__ __launch_bounds__(512, 1) void conv_x3_a3_mix_kernel(X3Args a) {
+    __shared__ __attribute__((aligned(1024))) char smem[X3_A3_LDS];
+    x3_stagger(a);
+    x3_stamp(a, 0);
+    const int b = blockIdx.x;
+    if (b < a.mix_b1) {
+        conv_x3_tile<256, false, false, 16, P, true, 256>(a, smem, xcd_remap(b, a.mix_b1), 0, a.nks, false);
+        return;
+    }
+    X3Args t = a;
+    if (b < a.mix_b2) {
+        t.m_base = a.mix_m1;
+        t.part_base = a.mix_p1;
+        conv_x3_tile<256, false, false, 16, P, true, 192>(t, smem, xcd_remap(b - a.mix_b1, a.mix_b2 - a.mix_b1), 0,
+                                                          a.nks, false);
+        return;
+    }
+    t.m_base = a.mix_m2;
+    t.part_base = a.mix_p2;
+    conv_x3_tile<256, false, false, 16, P, true, 160>(t, smem, xcd_remap(b - a.mix_b2, (int)gridDim.x - a.mix_b2), 0,
+                                                      a.nks, false);
 }
 
 // Split-K tail: the m-tiles of the last, partly filled round of a one-tile grid,
@@ -3552,7 +3595,63 @@ struct X3Choice {
     bool a3 = false;                   // conv_x3_a3_kernel<P> (256x256, 3-stage A ring)
     bool duo = false;                  // conv_x3_duo_kernel<1> (256x128, two 4-wave blocks per CU)
     int bm = 256;                      // rows per tile (192 / 160: conv_x3_a3_192 / _160_kernel<P>)
+    bool mix = false;                  // conv_x3_a3_mix_kernel<P>: the regions of x3_mix_plan
 };
+
+// The regions of a mixed-height launch (conv_x3_a3_mix_kernel) over M rows and
+// n_tiles column tiles on G CUs: a, b, c rounds of 256-, 192- and 160-row tiles,
+// G / n_tiles m-tiles to a round, minimising the 16-row blocks a CU runs, 16 a +
+// 12 b + 10 c, subject to (G / n_tiles) (256 a + 192 b + 160 c) >= M.  The three
+// heights cost the same per row, so plans of equal cost tie: the one with the most
+// 256-row rounds, then the most 192-row rounds (the fewest blocks), is taken; four
+// 192-row or eight 160-row rounds are three / five 256-row ones, so b <= 3, c <= 7.
+// Regions in that order; every region but the last non-empty one holds its whole
+// rounds, the last only the tiles that the rows left need.
+struct X3Mix {
+    int cost = 0;                      // 16-row blocks per CU; 0: no plan
+    int rounds[3] = {0, 0, 0};
+    long mt[3] = {0, 0, 0};            // m-tiles per region
+    long m_base[3] = {0, 0, 0};        // first output row
+    long part_base[3] = {0, 0, 0};     // first BN partial tile (128- / 96- / 80-row tiles)
+    long part_tiles = 0;               // BN partial tiles in all
+};
+static constexpr int X3_MIX_BM[3] = {256, 192, 160};
+static X3Mix x3_mix_plan(long M, int n_tiles, int G) {
+    X3Mix p;
+    if (M <= 0 || n_tiles <= 0 || G / n_tiles <= 0) return p;
+    const long R = G / n_tiles, need = (M + R - 1) / R;        // m-tiles per round, rows a CU column must cover
+    const long a_hi = (need + 255) / 256, a_lo = std::max<long>(0, (need - 3 * 192 - 7 * 160) / 256);
+    long best = -1, ba = 0, bb = 0, bc = 0;
+    for (long a = a_hi; a >= a_lo; --a)
+        for (long b = 3; b >= 0; --b)
+            for (long c = 0; c <= 7; ++c) {
+                if (256 * a + 192 * b + 160 * c < need) continue;
+                const long cost = 16 * a + 12 * b + 10 * c;
+                if (best < 0 || cost < best) { best = cost; ba = a; bb = b; bc = c; }
+                break;                                         // more 160-row rounds only cost more
+            }
+    if (best < 0 || best > (1L << 30)) return p;
+    p.cost = (int)best;
+    p.rounds[0] = (int)ba; p.rounds[1] = (int)bb; p.rounds[2] = (int)bc;
+    const int last = bc ? 2 : bb ? 1 : 0;
+    long row = 0, pt = 0;
+    for (int r = 0; r < 3; ++r) {
+        const long bm = X3_MIX_BM[r], left = M - row;
+        p.m_base[r] = row;
+        p.part_base[r] = pt;
+        p.mt[r] = r == last ? (left + bm - 1) / bm : p.rounds[r] * R;
+        const long rows = r == last ? left : p.mt[r] * bm;
+        row += rows;
+        pt += (rows + bm / 2 - 1) / (bm / 2);
+    }
+    p.part_tiles = pt;
+    return p;
+}
+// a mix launch's shape rule: packed operands, 256-wide output tiles, more than one
+// round of 256-row tiles (x3_choose; the A3 operand-size limits are the entry points')
+static bool x3_mix_ok(int k, long m_tiles, int P) {
+    return x3_packed(P) && k % 256 == 0 && m_tiles * (k / 256) > x3_cus();
+}
 // halo: 0 the halo-tile body cannot take the shape, 1 it can (HKP_TILE_HALO
 // forces it), 2 it is also the default (64 input channels: measured faster;
 // at 128 channels it ties the ring bodies, which then stay)
@@ -3580,6 +3679,8 @@ static X3Choice x3_choose(int k, long m_tiles, int nks, bool sk_ok, int policy, 
     // 192-row A3 tiles: packed operands with 256-divisible outputs; AUTO otherwise
     if (policy == HKP_TILE_192_A3 && (!x3_packed(P) || k % 256 != 0)) policy = HKP_TILE_AUTO;
     if (policy == HKP_TILE_160_A3 && (!x3_packed(P) || k % 128 != 0)) policy = HKP_TILE_AUTO;
+    // mixed tile heights: the same operands over more than one round of tiles; AUTO otherwise
+    if (policy == HKP_TILE_MIX_A3 && !x3_mix_ok(k, m_tiles, P)) policy = HKP_TILE_AUTO;
     if (policy != HKP_TILE_AUTO_A3 && policy != HKP_TILE_AUTO) return x3_choose_base(k, m_tiles, nks, sk_ok, policy, halo);
     X3Choice c = x3_choose_base(k, m_tiles, nks, sk_ok, HKP_TILE_AUTO, halo);
     if (c.bn == 256 && !c.sk && !c.halo && !c.pair) c.a3 = true;
@@ -3618,7 +3719,7 @@ static X3Choice x3_choose_base(int k, long m_tiles, int nks, bool sk_ok, int pol
     // the halo-tile body wherever the shape allows it, unless a tile body is forced
     if ((halo >= 1 && policy == HKP_TILE_HALO) ||
         (halo == 2 && (policy == HKP_TILE_AUTO || policy == HKP_TILE_256_TAIL || policy == HKP_TILE_256_A3 ||
-                       policy == HKP_TILE_192_A3 || policy == HKP_TILE_160_A3))) {
+                       policy == HKP_TILE_192_A3 || policy == HKP_TILE_160_A3 || policy == HKP_TILE_MIX_A3))) {
         X3Choice c{64, 16, true, false};
         c.halo = true;
         return c;
@@ -3649,6 +3750,11 @@ static X3Choice x3_choose_base(int k, long m_tiles, int nks, bool sk_ok, int pol
                 return c;
             }
             break;
+        case HKP_TILE_MIX_A3: {           // 256 / 192 / 160 x 256 regions in one launch (x3_choose checked)
+            X3Choice c{256, 16, false, false, false, true};
+            c.mix = true;
+            return c;
+        }
         default:
             break;
     }
@@ -3665,6 +3771,7 @@ static const X3Choice X3_STEM{64, 16, true, false};
 static int x3_kernel_name(const X3Choice& c, bool stem, int P, char* buf, int len) {
     if (c.halo) return snprintf(buf, len, "conv_x3_halo_kernel<%d>", P);
     if (c.duo) return snprintf(buf, len, "conv_x3_duo_kernel<%d>", P);
+    if (c.mix) return snprintf(buf, len, "conv_x3_a3_mix_kernel<%d>", P);
     if (c.a3)
         return snprintf(buf, len, c.bm == 192                  ? "conv_x3_a3_192_kernel<%d>"
                                   : c.bm == 160 && c.bn == 128 ? "conv_x3_a3_160x128_kernel<%d>"
@@ -3766,6 +3873,20 @@ static void launch_x3(int k, long m_tiles, int policy, int P, hipStream_t st, X3
         } else {
             x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL(conv_x3_halo_kernel<pc.value>, gh, dim3(512), 0, st, a); });
         }
+        return;
+    }
+    if (c.mix) {                           // one tile per block in up to three regions; no tail, no workspace
+        const X3Mix mp = x3_mix_plan(a.M, a.n_tiles, x3_cus());
+        X3Args t = a;
+        t.mix_b1 = (int)(mp.mt[0] * a.n_tiles);
+        t.mix_b2 = (int)((mp.mt[0] + mp.mt[1]) * a.n_tiles);
+        t.mix_m1 = (int)mp.m_base[1]; t.mix_m2 = (int)mp.m_base[2];
+        t.mix_p1 = (int)mp.part_base[1]; t.mix_p2 = (int)mp.part_base[2];
+        const dim3 gx((unsigned)((mp.mt[0] + mp.mt[1] + mp.mt[2]) * a.n_tiles));
+        x3_dispatch_p(P, [&](auto pc) {
+            if constexpr (x3_packed(pc.value))
+                hipLaunchKernelGGL(conv_x3_a3_mix_kernel<pc.value>, gx, dim3(512), 0, st, t);
+        });
         return;
     }
     if (c.bm != 256) {                     // one tile per block, no split-K tail
@@ -3870,7 +3991,7 @@ static bool x3_offsets_fit(long n, long h, long w, long cstride, long k, long rs
 }
 
 static int check_tile(const hkp_conv_desc* d, const char* who) {
-    HKP_CHECK_ARG(d->tile >= HKP_TILE_AUTO && d->tile <= HKP_TILE_160_A3, "%s: unknown tile policy %d", who,
+    HKP_CHECK_ARG(d->tile >= HKP_TILE_AUTO && d->tile <= HKP_TILE_MIX_A3, "%s: unknown tile policy %d", who,
                   d->tile);
     HKP_CHECK_ARG(d->tile != HKP_TILE_RESERVED_7 && d->tile != HKP_TILE_RESERVED_8 && d->tile != HKP_TILE_RESERVED_14,
                   "%s: tile policy %d is retired (a persistent conv body, measured slower)", who, d->tile);
@@ -4290,10 +4411,74 @@ extern "C" int hkp_conv2d_fwd_stem_x3_image(const hkp_conv_desc* d, const void* 
 // rows per BN statistic tile of a packed forward conv (see hulkkp.h)
 extern "C" int32_t hkp_conv_x3_stat_tile_rows(const hkp_conv_desc* d, int32_t op) {
     HKP_CHECK_ARG(d, "hkp_conv_x3_stat_tile_rows: null descriptor");
-    const bool packed = op == HKP_KOP_FWD_X3 || op == HKP_KOP_FWD_X3_W16 || op == HKP_KOP_FWD_X3_X16;
-    if (packed && d->tile == HKP_TILE_192_A3 && d->k % 256 == 0) return 96;
-    if (packed && d->tile == HKP_TILE_160_A3 && d->k % 128 == 0) return 80;
-    return 128;
+    if (op != HKP_KOP_FWD_X3 && op != HKP_KOP_FWD_X3_W16 && op != HKP_KOP_FWD_X3_X16 && op != HKP_KOP_FWD_F16) return 128;
+    int32_t seg[6];
+    const int n = hkp_conv_x3_stat_layout(d, op, seg);
+    return n < 0 ? n : seg[0];         // a mix launch's list has several (hkp_conv_x3_stat_layout)
+}
+
+// the body a forward launch with this descriptor runs (the launcher's x3_choose), and M
+static int x3_fwd_choice(const hkp_conv_desc* d, int32_t op, bool sk, X3Choice* c, long* m_out, const char* who) {
+    int ho, wo;
+    int rc = hkp_conv_out_hw(d, &ho, &wo);
+    if (rc) return rc;
+    rc = check_tile(d, who);
+    if (rc) return rc;
+    HKP_CHECK_ARG(op == HKP_KOP_FWD_X3 || op == HKP_KOP_FWD_X3_W16 || op == HKP_KOP_FWD_X3_X16 || op == HKP_KOP_FWD_F16,
+                  "%s: not a forward conv op %d", who, op);
+    const int P = op == HKP_KOP_FWD_X3 ? 3 : op == HKP_KOP_FWD_X3_W16 ? 2 : op == HKP_KOP_FWD_X3_X16 ? 4 : 1;
+    const long m = (long)d->n * ho * wo;
+    const int cg = x3_packed(P) ? 32 : 64;
+    const int nks = d->r * d->s * (d->c / cg);
+    const bool halo = halo_shape(d->stride, d->r, d->s, d->pad, d->dilation, ho, wo, d->k) &&
+                      (long)d->n * d->h * d->w * (d->c / cg * 64L) + 64 < (1L << 32);
+    *c = x3_choose(d->k, (m + 255) / 256, nks, sk, d->tile, x3_halo_level(halo, d->c / cg, P), P);
+    *m_out = m;
+    return HKP_OK;
+}
+
+// the segments of a forward conv's BN partial list (see hulkkp.h)
+extern "C" int32_t hkp_conv_x3_stat_layout(const hkp_conv_desc* d, int32_t op, int32_t* segments) {
+    HKP_CHECK_ARG(d && segments, "hkp_conv_x3_stat_layout: null argument");
+    X3Choice c{64, 16, true, false};
+    long m = 0;
+    const int rc = x3_fwd_choice(d, op, true, &c, &m, "hkp_conv_x3_stat_layout");
+    if (rc) return rc < 0 ? rc : -rc;
+    for (int i = 0; i < 6; ++i) segments[i] = 0;
+    if (c.mix) {
+        const X3Mix mp = x3_mix_plan(m, d->k / 256, x3_cus());
+        int n = 0;
+        for (int r = 0; r < 3; ++r) {
+            if (mp.mt[r] == 0) continue;
+            const long end = r == 2 ? mp.part_tiles : mp.part_base[r + 1];
+            segments[2 * n] = X3_MIX_BM[r] / 2;
+            segments[2 * n + 1] = (int32_t)(end - mp.part_base[r]);
+            ++n;
+        }
+        return n;
+    }
+    // the halo-tile and DUO bodies write 128-row partials whatever the policy asked for
+    const int rows = c.halo || c.duo || c.bm == 256 ? 128 : c.bm / 2;
+    segments[0] = rows;
+    segments[1] = (int32_t)((m + rows - 1) / rows);
+    return 1;
+}
+
+// the regions of a mixed-height launch (see hulkkp.h): pure host arithmetic
+extern "C" int32_t hkp_conv_x3_mix_plan(int64_t m, int32_t n_tiles, int32_t cus, int32_t* out) {
+    HKP_CHECK_ARG(out && m > 0 && m < (1L << 31) && n_tiles > 0 && cus > 0, "hkp_conv_x3_mix_plan: bad args");
+    const X3Mix mp = x3_mix_plan(m, n_tiles, cus);
+    out[0] = mp.cost;
+    int n = 0;
+    for (int r = 0; r < 3; ++r) {
+        out[1 + r] = mp.rounds[r];
+        out[4 + r] = (int32_t)mp.mt[r];
+        out[7 + r] = (int32_t)mp.m_base[r];
+        out[10 + r] = (int32_t)mp.part_base[r];
+        n += mp.mt[r] > 0;
+    }
+    out[13] = (int32_t)mp.part_tiles;
+    return n;
 }
 
 // the kernel symbol a launch with this descriptor runs (see hulkkp.h)

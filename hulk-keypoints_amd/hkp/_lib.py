@@ -30,11 +30,12 @@ class ConvDesc(ctypes.Structure):
 # hkp_conv_desc.tile policies (include/hulkkp.h)
 (HKP_TILE_AUTO, HKP_TILE_NO_SK, HKP_TILE_SK, HKP_TILE_256, HKP_TILE_128_MF16, HKP_TILE_128_MF32, HKP_TILE_64_PAIR,
  HKP_TILE_RESERVED_7, HKP_TILE_RESERVED_8, HKP_TILE_256_TAIL, HKP_TILE_HALO, HKP_TILE_256_A3, HKP_TILE_AUTO_A3,
- HKP_TILE_DUO, HKP_TILE_RESERVED_14, HKP_TILE_192_A3, HKP_TILE_160_A3) = range(17)
+ HKP_TILE_DUO, HKP_TILE_RESERVED_14, HKP_TILE_192_A3, HKP_TILE_160_A3, HKP_TILE_MIX_A3) = range(18)
 # hkp_conv_kernel_name ops
 HKP_KOP_FWD_X3, HKP_KOP_DGRAD_X3, HKP_KOP_FWD_F16, HKP_KOP_STEM_X3, HKP_KOP_WGRAD_X3, HKP_KOP_FWD_X3_W16, \
     HKP_KOP_FWD_X3_X16, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8 = range(9)
 HKP_X3_W16, HKP_X3_ALL, HKP_X3_X16 = 2, 3, 4          # hkp_conv2d_fwd_x3_products product sets
+HKP_MIX_PLAN_LEN = 14                                 # hkp_conv_x3_mix_plan's out[]
 
 
 class PackJob(ctypes.Structure):
@@ -63,12 +64,17 @@ SIGNATURES = {
     "hkp_conv_out_hw": (ctypes.c_int, [_CD, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "hkp_conv_stat_tiles": (_I64, [_CD]),
     "hkp_conv_x3_stat_tile_rows": (_I32, [_CD, _I32]),
+    "hkp_conv_x3_stat_layout": (_I32, [_CD, _I32, ctypes.POINTER(_I32)]),
+    "hkp_conv_x3_mix_plan": (_I32, [_I64, _I32, _I32, ctypes.POINTER(_I32)]),
     "hkp_conv2d_fwd": (ctypes.c_int, [_CD, _P, _P, _P, _P, _P]),
     "hkp_bn_finalize": (ctypes.c_int, [_I32, _I64, _I64, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hkp_bn_finalize_workspace_bytes": (_I64, [_I32, _I64]),
     "hkp_bn_finalize_ws": (ctypes.c_int, [_I32, _I64, _I64, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64,
                                           _P]),
     "hkp_bn_stats": (ctypes.c_int, [_I32, _I64, _I64, _I32, _P, _P, _P, _I64, _P]),
+    "hkp_bn_finalize_seg": (ctypes.c_int, [_I32, _I64, _I32, ctypes.POINTER(_I32), _P, _P, _P, _F, _F, _P, _P, _P, _P,
+                                           _P, _P, _I64, _P]),
+    "hkp_bn_stats_seg": (ctypes.c_int, [_I32, _I64, _I32, ctypes.POINTER(_I32), _P, _P, _P, _I64, _P]),
     "hkp_bn_finalize_ranks": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hkp_bn_eval_params": (ctypes.c_int, [_I32, _P, _P, _P, _P, _F, _P, _P, _P]),
     "hkp_bn_apply": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P]),

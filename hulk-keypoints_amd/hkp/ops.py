@@ -10,7 +10,7 @@ import torch
 
 from ._lib import (HKP_KOP_DGRAD_X3, HKP_KOP_FWD_F16, HKP_KOP_FWD_X3, HKP_KOP_FWD_X3_W16, HKP_KOP_FWD_X3_X16,
                    HKP_KOP_STEM_X3, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8, HKP_KOP_WGRAD_X3, HKP_X3_ALL,
-                   HKP_LAYOUT_NCHW, HKP_LAYOUT_NHWC, HKP_TILE_160_A3, HKP_TILE_192_A3, ConvDesc, HkpError, call)
+                   HKP_LAYOUT_NCHW, HKP_LAYOUT_NHWC, HKP_TILE_160_A3, HKP_TILE_192_A3, HKP_TILE_MIX_A3, ConvDesc, HkpError, call)
 
 CONV_TILE_ROWS = 128  # BM of conv_fwd.hip (rows per BN statistic tile)
 
@@ -163,12 +163,17 @@ def channels_of(x):
     return x.shape[-1]
 
 
-def _stat_partials(n_rows, k, device, part_out, name, tile_rows=CONV_TILE_ROWS):
+def _stat_partials(n_rows, k, device, part_out, name, tile_rows=CONV_TILE_ROWS, segments=None):
     """BN tile partials [tiles, k, 2] of an n_rows-pixel conv output, tile_rows rows
     per tile: part_out (a caller's slice of a larger buffer) or a new tensor.  A
     tile size other than CONV_TILE_ROWS rides on the tensor (_hkp_tile_rows) to
-    bn_finalize / bn_stats."""
+    bn_finalize / bn_stats, and so does a segmented list's table (_hkp_segments:
+    ((rows, tiles), ...) of a mixed-height launch, hkp_conv_x3_stat_layout)."""
     tiles = (n_rows + tile_rows - 1) // tile_rows
+    if segments is not None and len(segments) > 1:
+        tiles = sum(t for _, t in segments)
+    else:
+        segments = None
     if part_out is None:
         part = torch.empty((tiles, k, 2), device=device, dtype=torch.float32)
     else:
@@ -178,12 +183,37 @@ def _stat_partials(n_rows, k, device, part_out, name, tile_rows=CONV_TILE_ROWS):
         part = part_out
     if tile_rows != CONV_TILE_ROWS:
         part._hkp_tile_rows = tile_rows
+    if segments is not None:
+        part._hkp_segments = tuple(segments)
     return part
 
 
 def stat_tile_rows(part):
     """Rows per BN statistic tile of conv partials (hkp_conv_x3_stat_tile_rows)."""
     return getattr(part, "_hkp_tile_rows", CONV_TILE_ROWS)
+
+
+def stat_segments(part):
+    """The (rows, tiles) segments of a mixed-height conv's partials, or None for a
+    list of one tile height."""
+    return getattr(part, "_hkp_segments", None)
+
+
+def conv_stat_layout(d, kop):
+    """hkp_conv_x3_stat_layout: the ((rows, tiles), ...) segments of a forward conv's
+    BN partial list."""
+    from ._lib import lib
+    seg = (ctypes.c_int32 * 6)()
+    n = lib().hkp_conv_x3_stat_layout(ctypes.byref(d), kop, seg)
+    if n < 1:
+        raise HkpError("hkp_conv_x3_stat_layout failed (rc=%d): %s"
+                       % (n, lib().hkp_last_error().decode(errors="replace")))
+    return tuple((seg[2 * i], seg[2 * i + 1]) for i in range(n))
+
+
+def _seg_table(segments):
+    flat = [v for rt in segments for v in rt]
+    return (ctypes.c_int32 * len(flat))(*flat)
 
 
 def conv2d_fwd_x3(xs, wp, stride=1, pad=0, dil=1, stats=True, out=None, part_out=None, sk=True, tile=0,
@@ -209,11 +239,12 @@ def conv2d_fwd_x3(xs, wp, stride=1, pad=0, dil=1, stats=True, out=None, part_out
     kop = HKP_KOP_FWD_X3 if products == HKP_X3_ALL else HKP_KOP_FWD_X3_W16 if products == 2 else HKP_KOP_FWD_X3_X16
     part = None
     if stats:
-        rows = CONV_TILE_ROWS
-        if tile in (HKP_TILE_192_A3, HKP_TILE_160_A3):      # 96- / 80-row statistic tiles (the library says)
-            from ._lib import lib
-            rows = lib().hkp_conv_x3_stat_tile_rows(ctypes.byref(d), kop)
-        part = _stat_partials(n * ho * wo, k, xs.device, part_out, "conv2d_fwd_x3.part_out", rows)
+        rows, segs = CONV_TILE_ROWS, None
+        if tile in (HKP_TILE_192_A3, HKP_TILE_160_A3, HKP_TILE_MIX_A3):
+            # 96- / 80-row statistic tiles, or a mixed-height launch's segments (the library says)
+            segs = conv_stat_layout(d, kop)
+            rows = segs[0][0]
+        part = _stat_partials(n * ho * wo, k, xs.device, part_out, "conv2d_fwd_x3.part_out", rows, segs)
 
     if products == HKP_X3_ALL:
         def launch():
@@ -550,6 +581,18 @@ def bn_finalize(part, count, gamma, beta, running_mean=None, running_var=None, n
                 raise HkpError("bn_finalize.%s: %d != C=%d" % (nm, t.numel(), c))
     if num_batches_tracked is not None:
         _need(num_batches_tracked, torch.int64, "bn_finalize.num_batches_tracked")
+    segs = stat_segments(part)
+    if segs is not None:
+        # a mixed-height conv's segmented list: the same merges, tile rows from the table
+        ws, nb = None, 0
+        if tiles >= two_level_tiles:
+            from ._lib import lib
+            nb = lib().hkp_bn_finalize_workspace_bytes(c, tiles)
+            ws = torch.empty((nb + 7) // 8, device=part.device, dtype=torch.float64)
+        call("hkp_bn_finalize_seg", c, count, len(segs), _seg_table(segs), _ptr(part), _ptr(gamma), _ptr(beta),
+             momentum, eps, _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), _ptr(ss), _ptr(mi),
+             _ptr(ws), nb, _stream())
+        return ss, mi
     if tiles >= two_level_tiles:
         # two-level merge (chunks of 128 tiles over [C/64][chunks] blocks, then per channel)
         from ._lib import lib
@@ -576,6 +619,10 @@ def bn_stats(part, count, two_level_tiles=FIN_TWO_LEVEL_TILES):
         from ._lib import lib
         nb = lib().hkp_bn_finalize_workspace_bytes(c, tiles)
         ws = torch.empty((nb + 7) // 8, device=part.device, dtype=torch.float64)
+    segs = stat_segments(part)
+    if segs is not None:
+        call("hkp_bn_stats_seg", c, count, len(segs), _seg_table(segs), _ptr(part), _ptr(st), _ptr(ws), nb, _stream())
+        return st
     call("hkp_bn_stats", c, count, tiles, stat_tile_rows(part), _ptr(part), _ptr(st), _ptr(ws), nb, _stream())
     return st
 

@@ -97,6 +97,15 @@ typedef struct hkp_conv_desc {
 #define HKP_TILE_160_A3 16            /* the same on 160 x 256 tiles (waves 2 x 4; 160 x 128 where
                                          Cout % 256 != 0, Cout % 128 == 0), BN partials per 80-row
                                          tile (tile_rows = 80) */
+#define HKP_TILE_MIX_A3 17            /* the same operands, Cout % 256 == 0, more than one round of 256 x 256
+                                         tiles: one launch whose blocks run 256-, then 192-, then
+                                         160-row A3 tiles (conv_x3_a3_mix_kernel), every CU tall
+                                         tiles first and one shorter tile last, so that the last
+                                         round is filled — hkp_conv_x3_mix_plan has the regions.  The
+                                         output bits are HKP_TILE_256_A3's; the BN partial list is
+                                         segmented (128-, 96-, 80-row tiles: hkp_conv_x3_stat_layout,
+                                         hkp_bn_finalize_seg).  No tail, no workspace.  Never AUTO's
+                                         own choice; other shapes plan as AUTO */
 
 /* output spatial size: (h + 2*pad - dilation*(r-1) - 1)/stride + 1 */
 int hkp_conv_out_hw(const hkp_conv_desc* d, int32_t* ho, int32_t* wo);
@@ -241,12 +250,33 @@ int hkp_bn_from_gram(int32_t k, int32_t c, int64_t count, const double* mean, co
 #define HKP_KOP_STEM_X3_IMAGE 7     /* hkp_conv2d_fwd_stem_x3_image, fp32 NCHW image */
 #define HKP_KOP_STEM_X3_IMAGE_U8 8  /* hkp_conv2d_fwd_stem_x3_image, uint8 NHWC batch */
 int32_t hkp_conv_kernel_name(const hkp_conv_desc* d, int32_t op, int32_t stream_k_ok, char* buf, int32_t len);
-/* Rows per BN statistic tile of a packed forward conv (op HKP_KOP_FWD_X3 / _W16 /
- * _X16) with this descriptor: 96 with d->tile == HKP_TILE_192_A3 (k % 256 == 0), 80
- * with HKP_TILE_160_A3 (k % 128 == 0), else 128 (hkp_conv_stat_tiles' tiles).  stat_partials then holds
+/* Rows per BN statistic tile of a forward conv (op HKP_KOP_FWD_X3 / _W16 / _X16 /
+ * _F16) with this descriptor, from the body the launcher picks for it: 96 on the
+ * 192-row A3 tiles (HKP_TILE_192_A3), 80 on the 160-row ones (HKP_TILE_160_A3), else
+ * 128 (hkp_conv_stat_tiles' tiles) — also where such a policy is routed to another
+ * body (the halo-tile body writes 128-row partials).  stat_partials then holds
  * ceil(M / rows) * k * 2 floats, and hkp_bn_finalize / _ws / hkp_bn_stats take
- * tile_rows = rows (src/resnet.py:46,49: the statistics are the same). */
+ * tile_rows = rows (src/resnet.py:46,49: the statistics are the same).  For a
+ * HKP_TILE_MIX_A3 launch this is the first segment's rows: use the layout below. */
 int32_t hkp_conv_x3_stat_tile_rows(const hkp_conv_desc* d, int32_t op);
+/* The BN partial list of that conv as segments: segments[2i] = rows per statistic
+ * tile of segment i, segments[2i + 1] = its tiles (room for 3 segments: 6 values);
+ * returns the segment count (1 for every body but the mixed-height launch, whose
+ * regions write ceil(region rows / (tile height / 2)) tiles each, in region
+ * order), or a negative HKP_ERR_*.  stat_partials holds sum(tiles) * k * 2
+ * floats; hkp_bn_finalize_seg / hkp_bn_stats_seg take the table as it is. */
+int32_t hkp_conv_x3_stat_layout(const hkp_conv_desc* d, int32_t op, int32_t* segments);
+/* The regions of a HKP_TILE_MIX_A3 launch over m output rows and n_tiles column tiles
+ * on cus CUs (host arithmetic only; the launcher uses the device's CU count): a, b, c
+ * rounds of 256-, 192-, 160-row tiles, cus / n_tiles m-tiles to a round, minimising
+ * 16 a + 12 b + 10 c subject to (cus / n_tiles) (256 a + 192 b + 160 c) >= m (ties:
+ * most 256-row rounds, then most 192-row ones); every region but the last
+ * non-empty one holds whole rounds, the last the tiles the rows left need.
+ * out[HKP_MIX_PLAN_LEN] = cost | rounds[3] | m-tiles[3] | first row[3] | first BN
+ * partial tile[3] | BN partial tiles in all.  Returns the non-empty regions (0: no
+ * plan, n_tiles > cus) or a negative HKP_ERR_*. */
+#define HKP_MIX_PLAN_LEN 14
+int32_t hkp_conv_x3_mix_plan(int64_t m, int32_t n_tiles, int32_t cus, int32_t* out);
 
 /* (The A/B instruments — hkp_debug_* — are not part of this library: they exist only
  * in the tools build, include/hulkkp_ab.h.) */
@@ -274,6 +304,22 @@ int hkp_bn_finalize_ws(int32_t c, int64_t count, int64_t tiles, int32_t tile_row
                        float* running_mean, float* running_var, int64_t* num_batches_tracked,
                        float* scale_shift, float* mean_invstd, void* workspace, int64_t ws_bytes,
                        hkp_stream_t stream);
+
+/* The same merges over a segmented tile list (a HKP_TILE_MIX_A3 conv's partials:
+ * hkp_conv_x3_stat_layout): segments[2i] = rows per tile, segments[2i + 1] = tiles of
+ * segment i, 1 <= nseg <= 3, a host table.  Every segment but the last is whole
+ * full tiles; the last segment's last tile holds the rows left of count.  Tiles
+ * merge in list order.  workspace == NULL: the one-kernel merge (hkp_bn_finalize),
+ * else the two-level one (hkp_bn_finalize_ws; hkp_bn_finalize_workspace_bytes(c,
+ * sum of tiles)).  nseg == 1 is hkp_bn_finalize / _ws / hkp_bn_stats itself: the
+ * same kernels, the same bits. */
+int hkp_bn_finalize_seg(int32_t c, int64_t count, int32_t nseg, const int32_t* segments, const float* partials,
+                        const float* gamma, const float* beta, float momentum, float eps,
+                        float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                        float* scale_shift, float* mean_invstd, void* workspace, int64_t ws_bytes,
+                        hkp_stream_t stream);
+int hkp_bn_stats_seg(int32_t c, int64_t count, int32_t nseg, const int32_t* segments, const float* partials,
+                     double* stats, void* workspace, int64_t ws_bytes, hkp_stream_t stream);
 
 /* SyncBN for data-parallel ranks (caveat D5: train-mode BN makes a
  * shard's outputs depend on the shard; torch.nn.SyncBatchNorm's forward

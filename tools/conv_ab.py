@@ -6,6 +6,9 @@ compare separate processes).  Reports the kernel each policy runs and the
 largest output difference between policies (fp32 summation order).
 
     python tools/conv_ab.py [--tiles 0,3,4] [--shapes c4_l4_c1,...] [--rounds 7] [--iters 10]
+
+The mixed-height launch (HKP_TILE_MIX_A3) against the plan's choice on the C2 shapes
+it takes:  python tools/conv_ab.py --tiles 0,17 --shapes layer3,layer4,l4c1
 """
 import argparse
 import os
@@ -28,6 +31,8 @@ SHAPES = {
     "l3c1": ("x3", 32, 60, 80, 128, 256, 3, 1, 1, 1),           # layer3 conv1 (128 -> 256)
     "l3ds": ("x3", 32, 60, 80, 128, 256, 1, 1, 0, 1),
     "t2": ("x3", 8, 60, 80, 128, 128, 3, 1, 1, 1),             # layer2 at batch 8
+    "b16_l3": ("x3", 16, 60, 80, 256, 256, 3, 1, 2, 2),        # batch 64 over 4 GPUs: 300 / 600 256-row tiles
+    "b16_l4": ("x3", 16, 60, 80, 512, 512, 3, 1, 4, 4),
     "t1": ("x3", 8, 120, 160, 64, 64, 3, 1, 1, 1),             # layer1 at batch 8
     "l4c1": ("x3", 32, 60, 80, 256, 512, 3, 1, 2, 2),           # layer4 conv1 (256 -> 512)
     "l4ds": ("x3", 32, 60, 80, 256, 512, 1, 1, 0, 1),

@@ -8,6 +8,10 @@ median ms and the chosen one — the fastest, kept at the planner (0) unless the
 fastest beats it by more than HYST).
 
     python tools/tile_sweep.py [--workloads c2,b8,c4,c5] [--rounds 5] [--iters 4] [--out PATH]
+
+``--policies 17`` re-measures (every live policy, as above) only the shapes on which
+one of these policies runs a kernel of its own, and leaves the other entries as
+they are.
 """
 import argparse
 import json
@@ -19,8 +23,9 @@ sys.path[:0] = [REPO, os.path.join(REPO, "hulk-keypoints_amd")]
 
 import torch  # noqa: E402
 
-# every live HKP_TILE_* (7, 8, 14 retired; 12 = AUTO_A3, the round-4 planner; 15 / 16 = 192- / 160-row A3, x3 only)
-TILES = {"x3": (0, 1, 2, 3, 4, 5, 6, 9, 11, 12, 15, 16), "f16": (0, 1, 2, 3, 4, 5, 6, 9, 11, 12, 13),
+# every live HKP_TILE_* (7, 8, 14 retired; 12 = AUTO_A3, the round-4 planner; 15 / 16 = 192- / 160-row A3 and
+# 17 = the mixed-height A3 launch, x3 only)
+TILES = {"x3": (0, 1, 2, 3, 4, 5, 6, 9, 11, 12, 15, 16, 17), "f16": (0, 1, 2, 3, 4, 5, 6, 9, 11, 12, 13),
          "f16bn": (0, 3, 4, 5, 6, 11, 13)}
 HYST = 0.015
 
@@ -86,7 +91,7 @@ def key_of(s):
     return "|".join(str(v) for v in s)
 
 
-def time_shape(s, rounds, iters):
+def time_shape(s, rounds, iters, only=None):
     from hkp import ops
     kind, n, h, w, cin, cout, k, st, pd, dl = s
     dev = torch.device("cuda", 0)
@@ -123,6 +128,8 @@ def time_shape(s, rounds, iters):
     # the unfused one runs it (same tiles, same bits — test_fused_input_bn_network_bitexact)
     if names[0].startswith("conv_x3_halo"):
         tiles = [0]
+    if only is not None and not [t for t in tiles if t in only and t != 0]:
+        return None                        # --policies: none of them has a kernel of its own here
     times = {t: [] for t in tiles}
     for _ in range(rounds):
         for t in tiles:
@@ -149,6 +156,7 @@ def main():
     ap.add_argument("--workloads", default="c2,b8,c3,c4,c5")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--policies", default=None, help="re-measure only the shapes these policies run a kernel of their own on")
     ap.add_argument("--out", default=os.path.join(REPO, "hulk-keypoints_amd", "hkp", "tile_plan.json"))
     args = ap.parse_args()
     table = {}
@@ -157,8 +165,11 @@ def main():
     for wl in args.workloads.split(","):
         shapes = record(wl)
         print("%s: %d conv shapes" % (wl, len(shapes)), flush=True)
+        only = None if args.policies is None else [int(t) for t in args.policies.split(",")]
         for s in shapes:
-            med = time_shape(s, args.rounds, args.iters)
+            med = time_shape(s, args.rounds, args.iters, only)
+            if med is None:
+                continue
             pick = choose(med)
             table[key_of(s)] = {"ms": {str(t): round(v, 5) for t, v in med.items()}, "tile": pick,
                                 "workloads": sorted(set(table.get(key_of(s), {}).get("workloads", []) + [wl]))}
