@@ -1,7 +1,9 @@
 """config.py of the reference (config.py:1-6), same names and defaults.
 
 Additive keys (defaults reproduce the reference): BACKBONE, LOSS
-('bce' is what train.py:25 uses; 'mse' is train.py:13's unused MSE).
+('bce' is what train.py:25 uses; 'mse' is train.py:13's unused MSE),
+DOMAIN_RANDOMIZATION (True: the train set goes through the reference's commented-out
+augmentation pipeline, dataset.py:18-31, on the GPU) and DR_SEED (its seed).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -12,3 +14,5 @@ batch_size = 4
 
 BACKBONE = "resnet34"
 LOSS = "bce"
+DOMAIN_RANDOMIZATION = False
+DR_SEED = 0

@@ -51,6 +51,27 @@ class AdamTensor(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+# hkp_aug_stage.kind and the fixed sizes of the augmentation ABI (include/hulkkp.h)
+HKP_AUG_LUT, HKP_AUG_HSV, HKP_AUG_BLUR, HKP_AUG_NOISE = 1, 2, 3, 4
+HKP_AUG_MAX_STAGES = 8
+HKP_AUG_GAUSS_TABLE = 4096
+HKP_AUG_TILE_H, HKP_AUG_TILE_W = 16, 64
+
+
+class AugStage(ctypes.Structure):
+    """hkp_aug_stage (hkp_augment_u8)."""
+    _fields_ = [("kind", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("f", ctypes.c_float * 3),
+                ("key", ctypes.c_uint32 * 2), ("reserved1", ctypes.c_int32)]
+
+
+class AugProgram(ctypes.Structure):
+    """hkp_aug_program (hkp_augment_u8)."""
+    _fields_ = [("nstages", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7),
+                ("stages", AugStage * HKP_AUG_MAX_STAGES)]
+
+
+assert ctypes.sizeof(AugStage) == 32 and ctypes.sizeof(AugProgram) == 288
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -143,6 +164,8 @@ SIGNATURES = {
     # hybrid JPEG decode, device half (the geometry struct: hkp.jpeg.Geom)
     "hkp_jpeg_planes_bytes": (_I64, [_P]),
     "hkp_jpeg_reconstruct": (ctypes.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _P]),
+    # domain randomisation (programs_host: AugProgram array on the host, programs: its device copy)
+    "hkp_augment_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, ctypes.POINTER(AugProgram), _P, _P, _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

@@ -528,6 +528,26 @@ def images_u8_to_nchw(img):
     return x
 
 
+def augment_u8(img, plan):
+    """Domain randomisation (dataset.py:18-31): img uint8 [B,H,W,3] BGR and the batch's
+    hkp.augment.Plan (one program per image) → the augmented uint8 [B,H,W,3], one
+    launch on the current stream.  The plan's arrays are uploaded on that stream."""
+    _need(img, torch.uint8, "augment_u8.img", 4)
+    n, h, w, c = img.shape
+    if c != 3:
+        raise HkpError("augment_u8: img must be [B,H,W,3], got %s" % (tuple(img.shape),))
+    if n < 1 or h < 3 or w < 3:
+        raise HkpError("augment_u8: need B >= 1 and H, W >= 3 (reflect-101 borders), got %s" % (tuple(img.shape),))
+    if getattr(plan, "n", None) != n:
+        raise HkpError("augment_u8: the plan holds %s programs for a batch of %d" % (getattr(plan, "n", None), n))
+    progs, luts = plan.device_arrays(img.device)
+    table = plan.table.on(img.device)
+    out = torch.empty_like(img)
+    call("hkp_augment_u8", n, h, w, _ptr(img), _ptr(out), plan.programs, _ptr(progs), _ptr(luts), _ptr(table),
+         _stream())
+    return out
+
+
 def heat_overlay(heat, img, yx):
     """Prediction.plot's picture on the GPU: heat [B,K,H,W] fp32,
     img uint8 [B,H,W,3] BGR, yx int32 [B,K,2] argmax → uint8 [B, H*K/2, 2W, 3]

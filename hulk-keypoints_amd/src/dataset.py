@@ -49,6 +49,16 @@ class Compose:
 transform = Compose([_to_tensor])
 
 
+def domain_randomization(seed=0, random_order=True, ops=None):
+    """The reference's commented-out transform (dataset.py:18-31): the eight imgaug
+    colour / blur / noise augmenters in random order, then ToTensor — here
+    hkp.augment.DomainRandomization (one HIP kernel, csrc/augment.hip) composed
+    with ToTensor.  For the device data path pass the DomainRandomization object
+    itself: DeviceBatches(..., augment=DomainRandomization(seed))."""
+    from hkp.augment import DomainRandomization
+    return Compose([DomainRandomization(seed=seed, random_order=random_order, ops=ops), _to_tensor])
+
+
 def imread_bgr(path):
     """cv2.imread (BGR uint8 HWC) when OpenCV is installed, else PIL converted to BGR."""
     try:
@@ -222,15 +232,22 @@ class DeviceBatches:
     worker) into pinned memory.  Each batch is copied with non_blocking=True on a
     side stream while the previous batch computes; the consumer's stream waits on
     an event.  `shuffle` uses a seeded permutation per epoch (train.py:61-67
-    shuffles); batches come in order for any worker count."""
+    shuffles); batches come in order for any worker count.
+
+    augment: a hkp.augment.DomainRandomization (dataset.py:18-31), or None.  When
+    set, each batch is augmented on the copy stream right after its copy / JPEG
+    reconstruct, image b under the program of (augment.seed, this epoch, its dataset
+    index) — the same pixels for any batch size, worker count or decode mode.
+    Labels are untouched (every operator keeps the geometry)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, drop_last=False, device="cuda", workers=0,
-                 prefetch=4, decode="host"):
+                 prefetch=4, decode="host", augment=None):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
         self.ds, self.bs, self.shuffle, self.seed, self.drop_last = dataset, batch_size, shuffle, seed, drop_last
         self.device = torch.device(device)
         self.workers, self.prefetch, self.decode = workers, prefetch, decode
+        self.augment = augment
         self.epoch = 0
         self._loader = None
         self._sampler = _EpochBatches()
@@ -269,15 +286,18 @@ class DeviceBatches:
     def __iter__(self):
         n = len(self.ds)
         order = (np.random.default_rng(self.seed + self.epoch).permutation(n) if self.shuffle else np.arange(n))
+        epoch = self.epoch
         self.epoch += 1
         batches = [order[i:i + self.bs] for i in range(0, n, self.bs)]
         if self.drop_last and batches and len(batches[-1]) < self.bs:
             batches.pop()
         copy_stream = torch.cuda.Stream(self.device)
         host = self._host_batches(batches)
+        staged = iter(batches)                 # host batches come in this order
 
         def stage():
             b = next(host)
+            idx = next(staged)
             with torch.cuda.stream(copy_stream):
                 if b[0] == "img":
                     buf, uv = b[1], b[2]
@@ -289,6 +309,10 @@ class DeviceBatches:
                     g = jpeg.Geom.from_buffer_copy(gbytes)
                     img = jpeg.reconstruct(coefs.to(self.device, non_blocking=True),
                                            qt.to(self.device, non_blocking=True), g, coefs.shape[0])
+                if self.augment is not None:
+                    plan = self.augment.plan(idx, epoch)
+                    img = ops.augment_u8(img, plan)
+                    buf = (buf, plan)          # the plan's pinned arrays live as long as the batch's
                 uvd = uv.to(self.device, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)

@@ -21,10 +21,11 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import BACKBONE, GAUSS_SIGMA, IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS, batch_size, epochs
+from config import (BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GAUSS_SIGMA, IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS,
+                    batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp.train import GradBucketer, broadcast_state
-from src.dataset import KeypointsDataset, transform
+from src.dataset import KeypointsDataset, domain_randomization, transform
 from src.model import KeypointsGauss
 
 use_cuda = True
@@ -107,8 +108,11 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
     save_dir = os.path.join(output_dir, dataset_dir)
     if _rank0():
         os.makedirs(save_dir, exist_ok=True)
+    # the reference switches its augmentation on by moving a '#' (dataset.py:15-31); here it is a config
+    # key, and only the train set is randomised.  The transform runs on the GPU: keep workers at 0.
+    train_transform = domain_randomization(seed=DR_SEED) if DOMAIN_RANDOMIZATION else transform
     train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir, "data/%s/train/keypoints" % dataset_dir,
-                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
+                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA,
                                      return_uv=True)
     test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,

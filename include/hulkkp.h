@@ -674,6 +674,61 @@ int64_t hkp_jpeg_planes_bytes(const hkpj_geom* g);
 int hkp_jpeg_reconstruct(int32_t n, const hkpj_geom* g, const int16_t* coefs, const uint16_t* qt, uint8_t* planes,
                          int64_t planes_bytes, uint8_t* out_bgr, hkp_stream_t stream);
 
+/* ---------------------------------------------- domain randomisation ---- */
+/* The reference's commented-out imgaug pipeline (src/dataset.py:18-31) on uint8
+ * [n][h][w][3] BGR batches.  One image's augmentation is a program: an ordered
+ * list of stages; after every stage the image is uint8 again (rint, half to
+ * even, then clamp to [0,255]).  All arithmetic is fp32 with every operation
+ * rounded on its own; transcendentals live in host-built tables (the LUTs, the
+ * blur weights, the Gaussian quantile table), so a numpy float32 restatement in
+ * the same order gives the same bits.
+ *
+ *   HKP_AUG_LUT    out_c = lut[c][v_c]; the stage in slot i of image b reads
+ *                  luts[b][i][c][256] (c in memory order B, G, R).  LinearContrast
+ *                  (:22), Add (:23), GammaContrast (:24), ChangeColorTemperature (:26).
+ *   HKP_AUG_HSV    one float RGB→HSV→RGB round trip: f[0] = hue shift in sectors
+ *                  (hue in [0,6)), S' = clamp(S * f[2] + f[1], 0, 255).
+ *                  AddToHueAndSaturation (:21), MultiplySaturation (:27).
+ *   HKP_AUG_BLUR   separable 5-tap blur, f[0..2] = w0, w1, w2 (w0 + 2 w1 + 2 w2 = 1),
+ *                  reflect-101 borders; at most one per program.  GaussianBlur (:25).
+ *   HKP_AUG_NOISE  n = gauss_table[x0 >> 20] * f[0], x0 = first word of
+ *                  Philox4x32-10(counter (y*w + x, 0, 0, 0), key), added to the
+ *                  three channels.  AdditiveGaussianNoise (:28).
+ */
+#define HKP_AUG_LUT 1
+#define HKP_AUG_HSV 2
+#define HKP_AUG_BLUR 3
+#define HKP_AUG_NOISE 4
+#define HKP_AUG_MAX_STAGES 8
+#define HKP_AUG_GAUSS_TABLE 4096   /* entries of gauss_table: fp32 quantiles of N(0,1) at (i + 0.5) / 4096 */
+#define HKP_AUG_TILE_H 16          /* one block's tile of one image (pixels) */
+#define HKP_AUG_TILE_W 64
+
+typedef struct hkp_aug_stage {
+    int32_t kind;        /* HKP_AUG_*                                   */
+    int32_t reserved0;
+    float f[3];          /* HSV: dh, add, mul; BLUR: w0, w1, w2; NOISE: scale */
+    uint32_t key[2];     /* NOISE: the Philox key                        */
+    int32_t reserved1;
+} hkp_aug_stage;         /* 32 bytes */
+
+typedef struct hkp_aug_program {
+    int32_t nstages;     /* 0 .. HKP_AUG_MAX_STAGES (0: copy)           */
+    int32_t reserved[7];
+    hkp_aug_stage stages[HKP_AUG_MAX_STAGES];
+} hkp_aug_program;       /* 288 bytes */
+
+/* img_out = programs applied to img_in, one launch for the batch.  programs_host
+ * and programs hold the same n programs: the host copy is validated here (stage
+ * counts, stage kinds, at most one BLUR) before anything is launched, the device
+ * copy is what the kernel reads.  luts: device uint8 [n][HKP_AUG_MAX_STAGES][3][256]
+ * (only the slots of LUT stages are read); gauss_table: device fp32
+ * [HKP_AUG_GAUSS_TABLE].  h, w >= 3 (reflect-101); img_out must not overlap img_in
+ * (the blur reads neighbours). */
+int hkp_augment_u8(int32_t n, int32_t h, int32_t w, const uint8_t* img_in, uint8_t* img_out,
+                   const hkp_aug_program* programs_host, const hkp_aug_program* programs, const uint8_t* luts,
+                   const float* gauss_table, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
