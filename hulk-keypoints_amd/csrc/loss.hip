@@ -5,8 +5,12 @@
 //                    tensor or recomputed in registers from (u, v); MSE (train.py:13)
 //                    selectable.  fp64 loss, fp64 per-element gradient:
 //                      BCE  l = (y-1)*max(log1p(-p),-100) - y*max(log p,-100)
-//                           g = (p-y) / max((1-p)*p, 1e-12) / N
+//                           g = (p-y) / max((1-p)*p, EPS) / N
 //                      MSE  l = (p-y)^2,  g = 2 (p-y) / N
+//                    EPS is ATen's binary_cross_entropy_backward constant, a
+//                    float (`constexpr float EPSILON = 1e-12`) widened to double:
+//                    9.99999996e-13.  The double 1e-12 is 4e-9 larger, enough to
+//                    move the fp32 gradient of a saturated pixel by one ulp.
 //                    then cast to fp32 (the .double() cast's backward).
 //  * hkp_head_bwd    sigmoid backward (g*(1-p))*p (model.py:21) fused with the
 //                    adjoint of the align_corners=True upsample (resnet_dilated.py:27)
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(256) void heat_loss_kernel(long total, int H, int W
         double l, g;
         if constexpr (KIND == HKP_LOSS_BCE) {
             l = (y - 1.0) * fmax(log1p(-x), -100.0) - y * fmax(log(x), -100.0);
-            g = (x - y) / fmax((1.0 - x) * x, 1e-12) * inv_n;
+            g = (x - y) / fmax((1.0 - x) * x, (double)1e-12f) * inv_n;
         } else {
             l = (x - y) * (x - y);
             g = 2.0 * inv_n * (x - y);
@@ -108,7 +112,12 @@ __global__ void loss_finalize_kernel(int nparts, double inv_n, const double* __r
 // Each high-res element is read by <= 2 pass-1 threads (vs ~4 node gathers that
 // each recomputed every candidate's lerp in the direct form).
 __device__ __forceinline__ void cand_range(int i, int in, int out, float inv, int* o0, int* o1) {
-    if (out != in) {
+    if (in == 1) {
+        // a single source node: every output reads it (there is no inverse scale
+        // to bound the candidates with), still summed in ascending output order
+        *o0 = 0;
+        *o1 = out - 1;
+    } else if (out != in) {
         *o0 = max(0, (int)floorf((float)(i - 1) * inv) - 1);
         *o1 = min(out - 1, (int)ceilf((float)(i + 1) * inv) + 1);
     } else {

@@ -781,8 +781,13 @@ def bn_relu_maxpool(y, ss, split=0, route=False, keep_fp32=True):
     return out
 
 
+HEAD_FC_LDS_FLOATS = 16384  # hkp_head_fc's k*c limit (head.hip: its [K][C] rows in 64 KiB of LDS)
+
+
 def head_fc(feat, w_kc, bias_k):
-    """feat NHWC [N,h,w,C]; w [K,C]; bias [K] → lowres NCHW [N,K,h,w]."""
+    """feat NHWC [N,h,w,C]; w [K,C]; bias [K] → lowres NCHW [N,K,h,w].
+    hkp_head_fc stages its rows in 64 KiB of LDS (K*C <= 16384 floats): more rows
+    than that (C = 2048 with K > 8) run in row chunks, concatenated along K."""
     _need(feat, torch.float32, "head_fc.feat", 4)
     _need(w_kc, torch.float32, "head_fc.w", 2)
     _need(bias_k, torch.float32, "head_fc.bias", 1)
@@ -790,6 +795,13 @@ def head_fc(feat, w_kc, bias_k):
     k = w_kc.shape[0]
     if w_kc.shape[1] != c or bias_k.numel() != k:
         raise HkpError("head_fc: weight %s / bias %s do not match C=%d" % (tuple(w_kc.shape), bias_k.numel(), c))
+    if k * c > HEAD_FC_LDS_FLOATS:
+        rows = min(16, HEAD_FC_LDS_FLOATS // max(c, 1))
+        if rows == 0:
+            raise HkpError("head_fc: C=%d: one row does not fit the kernel's LDS (%d floats)"
+                           % (c, HEAD_FC_LDS_FLOATS))
+        # (row slices of contiguous [K,C] / [K] tensors are contiguous)
+        return torch.cat([head_fc(feat, w_kc[k0:k0 + rows], bias_k[k0:k0 + rows]) for k0 in range(0, k, rows)], 1)
     low = torch.empty((n, k, h, w), device=feat.device, dtype=torch.float32)
     call("hkp_head_fc", n, h * w, c, k, _ptr(feat), _ptr(w_kc), _ptr(bias_k), _ptr(low), _stream())
     return low

@@ -641,6 +641,10 @@ int hkp_maxpool_bwd(int32_t n, int32_t h, int32_t w, int32_t c, const float* dpo
 /* Loss over the heatmaps (train.py:21,25; MSE train.py:13) in fp64: loss (device
  * double), dheat = dL/dheat as fp32 (nullable).  Target: dense fp64 `target`
  * [n,k,H,W], or NULL to recompute the Gaussian from uv/sigma (dataset.py:36-44).
+ * BCE clamps as ATen does: the logs at -100, and the gradient's denominator
+ * (1-p)*p at ATen's `constexpr float EPSILON = 1e-12` widened to double
+ * ((double)1e-12f = 9.99999996e-13, not the double 1e-12), so dheat keeps
+ * nn.BCELoss's bits on saturated pixels (p of 0, 1 or within 1e-12 of either).
  * workspace: hkp_heat_loss_workspace() bytes. */
 int64_t hkp_heat_loss_workspace(void);
 int hkp_heat_loss(int32_t n, int32_t k, int32_t H, int32_t W, int32_t loss_kind, const float* heat,
@@ -650,7 +654,8 @@ int hkp_heat_loss(int32_t n, int32_t k, int32_t H, int32_t W, int32_t loss_kind,
 /* dlow = upsample-adjoint( dheat * (1-heat) * heat ) (sigmoid backward fused;
  * heat NULL = dheat is already the pre-sigmoid gradient): a row gather into
  * `workspace` (hkp_head_bwd_workspace bytes: [n*k][H][w] floats), then a column
- * gather — the direct double sum's loop order, so the same bits. */
+ * gather — the direct double sum's loop order, so the same bits.  Needs H >= h
+ * and W >= w; h or w of 1 is fine (that one node takes every output's gradient). */
 int64_t hkp_head_bwd_workspace(int32_t n, int32_t k, int32_t w, int32_t H);
 int hkp_head_bwd(int32_t n, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W, const float* dheat,
                  const float* heat, float* dlow, void* workspace, int64_t ws_bytes, hkp_stream_t stream);

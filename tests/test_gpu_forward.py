@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _tail_ref import upsample_emulated
 from oracle import cpu_ref, recipe
 
 pytestmark = pytest.mark.gpu
@@ -99,32 +100,6 @@ def test_bn_relu_maxpool(cuda_device):
     ref = F.max_pool2d(F.relu(y.permute(0, 3, 1, 2) * ss[:64, None, None] + ss[64:, None, None]), 3, 2, 1)
     out = ops.bn_relu_maxpool(y.to(cuda_device), ss.to(cuda_device))
     assert (out.cpu().permute(0, 3, 1, 2) - ref).abs().max() < 1e-6
-
-
-def upsample_emulated(low, H, W):
-    """The exact fp32 arithmetic of ATen's CPU bilinear align_corners=True kernel
-    as measured on the fixture-generating host (torch 2.10, contracted form
-    t = fma(x0, l0, x1*l1)); host-ISA independent, so it pins the GPU bitwise."""
-    f = np.float32
-    x = low.numpy().astype(f)
-    h, w = x.shape[2:]
-
-    def idx(inn, out):
-        scale = f(inn - 1) / f(out - 1)
-        src = (scale * np.arange(out, dtype=f)).astype(f)
-        i0 = np.minimum(np.floor(src).astype(np.int64), inn - 1)
-        l1 = np.clip((src - i0.astype(f)).astype(f), f(0), f(1))
-        return i0, i0 + (i0 < inn - 1), (f(1) - l1).astype(f), l1
-
-    def fma(a, b, c):
-        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f)
-
-    h0, h1, lh0, lh1 = idx(h, H)
-    w0, w1, lw0, lw1 = idx(w, W)
-
-    def row(hi):
-        return fma(x[:, :, hi][..., w0], lw0, (x[:, :, hi][..., w1] * lw1).astype(f))
-    return torch.from_numpy(fma(row(h0), lh0[:, None], (row(h1) * lh1[:, None]).astype(f)))
 
 
 @pytest.mark.parametrize("shape", [(2, 4, 12, 16, 96, 128), (1, 4, 60, 80, 480, 640), (2, 3, 10, 13, 75, 100)])
