@@ -3,7 +3,10 @@
 Additive keys (defaults reproduce the reference): BACKBONE, LOSS
 ('bce' is what train.py:25 uses; 'mse' is train.py:13's unused MSE),
 DOMAIN_RANDOMIZATION (True: the train set goes through the reference's commented-out
-augmentation pipeline, dataset.py:18-31, on the GPU) and DR_SEED (its seed).
+augmentation pipeline, dataset.py:18-31, on the GPU) and DR_SEED (its seed),
+GEOMETRIC_AUGMENTATION (True: the train set's images and labels go through
+hkp.geometry.GeometricAugmentation — rotation, scale, translation, flips; not in the
+reference), GA_SEED (its seed) and GA_PARAMS (its other keyword arguments).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -16,3 +19,6 @@ BACKBONE = "resnet34"
 LOSS = "bce"
 DOMAIN_RANDOMIZATION = False
 DR_SEED = 0
+GEOMETRIC_AUGMENTATION = False
+GA_SEED = 0
+GA_PARAMS = {}

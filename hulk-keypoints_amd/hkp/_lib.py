@@ -72,6 +72,20 @@ class AugProgram(ctypes.Structure):
 
 assert ctypes.sizeof(AugStage) == 32 and ctypes.sizeof(AugProgram) == 288
 
+# the affine warp's ABI (include/hulkkp.h)
+HKP_WARP_BILINEAR, HKP_WARP_NEAREST = 0, 1
+HKP_WARP_BORDER_CONSTANT, HKP_WARP_BORDER_REPLICATE, HKP_WARP_BORDER_REFLECT101 = 0, 1, 2
+HKP_WARP_MAX_DIM = 16384
+
+
+class WarpXform(ctypes.Structure):
+    """hkp_warp_xform (hkp_warp_affine_u8): the inverse map dest -> source in Q16
+    and the fill colour (B, G, R, unused)."""
+    _fields_ = [("m", ctypes.c_int32 * 6), ("fill", ctypes.c_uint8 * 4), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(WarpXform) == 32
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -166,6 +180,9 @@ SIGNATURES = {
     "hkp_jpeg_reconstruct": (ctypes.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _P]),
     # domain randomisation (programs_host: AugProgram array on the host, programs: its device copy)
     "hkp_augment_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, ctypes.POINTER(AugProgram), _P, _P, _P, _P]),
+    # affine warp (xforms_host: WarpXform array on the host, xforms: its device copy)
+    "hkp_warp_affine_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(WarpXform), _P, _I32,
+                                          _I32, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

@@ -548,6 +548,51 @@ def augment_u8(img, plan):
     return out
 
 
+def warp_affine_u8(img, plan, out_hw=None):
+    """Batched affine warp (csrc/warp.hip): img uint8 [B,Hs,Ws,3] and the batch's
+    hkp.geometry.WarpPlan (one transform per image) → uint8 [B,H,W,3] with
+    (H, W) = out_hw, default the plan's own size; one launch on the current stream.
+    The plan's records are uploaded on that stream."""
+    from ._lib import HKP_WARP_BORDER_REFLECT101, HKP_WARP_MAX_DIM
+    _need(img, torch.uint8, "warp_affine_u8.img", 4)
+    n, hs, ws, c = img.shape
+    if c != 3:
+        raise HkpError("warp_affine_u8: img must be [B,H,W,3], got %s" % (tuple(img.shape),))
+    if n < 1 or not (1 <= hs <= HKP_WARP_MAX_DIM and 1 <= ws <= HKP_WARP_MAX_DIM):
+        raise HkpError("warp_affine_u8: need B >= 1 and H, W in 1..%d, got %s" % (HKP_WARP_MAX_DIM, tuple(img.shape)))
+    if getattr(plan, "n", None) != n:
+        raise HkpError("warp_affine_u8: the plan holds %s transforms for a batch of %d" % (getattr(plan, "n", None), n))
+    h, w = plan.hw if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if not (1 <= h <= HKP_WARP_MAX_DIM and 1 <= w <= HKP_WARP_MAX_DIM):
+        raise HkpError("warp_affine_u8: out_hw %dx%d outside 1..%d" % (h, w, HKP_WARP_MAX_DIM))
+    if plan.border == HKP_WARP_BORDER_REFLECT101 and (hs < 2 or ws < 2):
+        raise HkpError("warp_affine_u8: reflect101 needs a source of at least 2x2, got %dx%d" % (hs, ws))
+    xf = plan.device_array(img.device)
+    out = torch.empty((n, h, w, 3), device=img.device, dtype=torch.uint8)
+    call("hkp_warp_affine_u8", n, hs, ws, _ptr(img), h, w, _ptr(out), plan.xforms, _ptr(xf), plan.interp,
+         plan.border, _stream())
+    return out
+
+
+def resize_u8(img, h, w, interp="bilinear"):
+    """img uint8 [B,Hs,Ws,3] → [B,h,w,3]: the affine warp with the half-pixel-centre
+    resize matrix and replicated borders.  No antialiasing: large reductions alias."""
+    from . import geometry
+    from ._lib import HKP_WARP_MAX_DIM
+    if interp not in geometry.INTERP:
+        raise HkpError("resize_u8: unknown interp %r (known: %s)" % (interp, ", ".join(geometry.INTERP)))
+    _need(img, torch.uint8, "resize_u8.img", 4)
+    n, hs, ws, c = img.shape
+    if c != 3 or n < 1 or hs < 1 or ws < 1:
+        raise HkpError("resize_u8: img must be a non-empty [B,H,W,3], got %s" % (tuple(img.shape),))
+    h, w = int(h), int(w)
+    if not (1 <= h <= HKP_WARP_MAX_DIM and 1 <= w <= HKP_WARP_MAX_DIM):
+        raise HkpError("resize_u8: output %dx%d outside 1..%d" % (h, w, HKP_WARP_MAX_DIM))
+    m = geometry.resize_matrix(hs, ws, h, w)
+    plan = geometry.WarpPlan([m] * n, (h, w), interp=interp, border="replicate")
+    return warp_affine_u8(img, plan)
+
+
 def heat_overlay(heat, img, yx):
     """Prediction.plot's picture on the GPU: heat [B,K,H,W] fp32,
     img uint8 [B,H,W,3] BGR, yx int32 [B,K,2] argmax → uint8 [B, H*K/2, 2W, 3]

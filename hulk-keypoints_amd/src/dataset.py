@@ -102,7 +102,14 @@ def vis_gauss(gaussians):
 
 class KeypointsDataset(Dataset):
     def __init__(self, img_folder, labels_folder, num_keypoints, img_height, img_width, transform, gauss_sigma=8,
-                 return_uv=False, device="cuda"):
+                 return_uv=False, device="cuda", geometric=None):
+        """geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, the decoded
+        uint8 image and the host label go through it (on the GPU: keep num_workers=0)
+        before `transform`, under the sample's own index and the epoch of set_epoch();
+        the returned uv / Gaussians come from the transformed label."""
+        self.geometric = geometric
+        self.epoch = 0
+        self.device = device
         self.num_keypoints = num_keypoints
         self.img_height = img_height
         self.img_width = img_width
@@ -120,9 +127,21 @@ class KeypointsDataset(Dataset):
             self.labels.append(torch.from_numpy(label).to(device))
             self.labels_np.append(label.astype(np.float32))
 
+    def set_epoch(self, epoch):
+        """The epoch the geometric augmentation draws under (train.py's fit() calls it)."""
+        self.epoch = int(epoch)
+
+    def _decode(self, index):
+        """(uint8 HWC image, [K,2] labels on the device), through `geometric` when set."""
+        img = imread_bgr(self.imgs[index])
+        if self.geometric is None:
+            return img, self.labels[index]
+        img, uv = self.geometric(img, self.labels_np[index], index=index, epoch=self.epoch)
+        return img, torch.from_numpy(uv).to(self.device)
+
     def __getitem__(self, index):
-        img = self.transform(imread_bgr(self.imgs[index]))
-        labels = self.labels[index]
+        img, labels = self._decode(index)
+        img = self.transform(img)
         if self.return_uv:
             return img, labels.float()
         U = labels[:, 0]
@@ -132,7 +151,8 @@ class KeypointsDataset(Dataset):
 
     def raw(self, index):
         """(uint8 [H,W,3] BGR image as cv2.imread gives, fp32 [K,2] (u, v) on the device)."""
-        return imread_bgr(self.imgs[index]), self.labels[index].float()
+        img, labels = self._decode(index)
+        return img, labels.float()
 
     def __len__(self):
         return len(self.labels)
@@ -238,16 +258,26 @@ class DeviceBatches:
     set, each batch is augmented on the copy stream right after its copy / JPEG
     reconstruct, image b under the program of (augment.seed, this epoch, its dataset
     index) — the same pixels for any batch size, worker count or decode mode.
-    Labels are untouched (every operator keeps the geometry)."""
+    `augment` leaves the labels untouched (every one of its operators keeps the
+    geometry).
+
+    geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, each batch is
+    warped on the copy stream after its copy / JPEG reconstruct and before `augment`,
+    image b under the transform of (geometric.seed, this epoch, its dataset index,
+    its stored label), and the labels that are uploaded are plan.apply_uv(uv): moved
+    by the same transform, flip pairs exchanged, clipped to the image.  The
+    dataset's own `geometric` is not applied here (the decode workers read the raw
+    files)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, drop_last=False, device="cuda", workers=0,
-                 prefetch=4, decode="host", augment=None):
+                 prefetch=4, decode="host", augment=None, geometric=None):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
         self.ds, self.bs, self.shuffle, self.seed, self.drop_last = dataset, batch_size, shuffle, seed, drop_last
         self.device = torch.device(device)
         self.workers, self.prefetch, self.decode = workers, prefetch, decode
         self.augment = augment
+        self.geometric = geometric
         self.epoch = 0
         self._loader = None
         self._sampler = _EpochBatches()
@@ -309,6 +339,11 @@ class DeviceBatches:
                     g = jpeg.Geom.from_buffer_copy(gbytes)
                     img = jpeg.reconstruct(coefs.to(self.device, non_blocking=True),
                                            qt.to(self.device, non_blocking=True), g, coefs.shape[0])
+                if self.geometric is not None:
+                    gplan = self.geometric.plan(idx, epoch, uvs=uv, hw=(img.shape[1], img.shape[2]))
+                    img = ops.warp_affine_u8(img, gplan)
+                    uv = gplan.apply_uv(uv).pin_memory()
+                    buf = (buf, gplan, uv)     # the plan's pinned records and the labels live as long as the batch's
                 if self.augment is not None:
                     plan = self.augment.plan(idx, epoch)
                     img = ops.augment_u8(img, plan)

@@ -21,8 +21,8 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import (BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GAUSS_SIGMA, IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS,
-                    batch_size, epochs)
+from config import (BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GA_PARAMS, GA_SEED, GAUSS_SIGMA, GEOMETRIC_AUGMENTATION,
+                    IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp.train import GradBucketer, broadcast_state
 from src.dataset import KeypointsDataset, domain_randomization, transform
@@ -71,6 +71,8 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
     for epoch in range(epochs):
         if hasattr(getattr(train_data, "sampler", None), "set_epoch"):
             train_data.sampler.set_epoch(epoch)
+        if hasattr(getattr(train_data, "dataset", None), "set_epoch"):
+            train_data.dataset.set_epoch(epoch)     # the geometric augmentation draws per (seed, epoch, index)
         train_loss = 0.0
         i_batch = 0
         for i_batch, sample_batched in enumerate(train_data):
@@ -111,9 +113,13 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
     # the reference switches its augmentation on by moving a '#' (dataset.py:15-31); here it is a config
     # key, and only the train set is randomised.  The transform runs on the GPU: keep workers at 0.
     train_transform = domain_randomization(seed=DR_SEED) if DOMAIN_RANDOMIZATION else transform
+    geometric = None
+    if GEOMETRIC_AUGMENTATION:                      # images and labels together; the train set only
+        from hkp.geometry import GeometricAugmentation
+        geometric = GeometricAugmentation(seed=GA_SEED, **GA_PARAMS)
     train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir, "data/%s/train/keypoints" % dataset_dir,
                                      NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA,
-                                     return_uv=True)
+                                     return_uv=True, geometric=geometric)
     test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
                                     return_uv=True)

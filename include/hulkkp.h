@@ -734,6 +734,50 @@ int hkp_augment_u8(int32_t n, int32_t h, int32_t w, const uint8_t* img_in, uint8
                    const hkp_aug_program* programs_host, const hkp_aug_program* programs, const uint8_t* luts,
                    const float* gauss_table, hkp_stream_t stream);
 
+/* ------------------------------------------------------- affine warp ---- */
+/* Batched per-image affine warp of uint8 [n][hs][ws][3] into [n][h][w][3]: the
+ * geometric augmentation (rotation, scale, translation, shear, flips) and the
+ * resize are host-side matrix builders over it (hkp/geometry.py).  Integer pixel
+ * coordinates are pixel centres (as for the labels and hkp_gauss_target).  The
+ * arithmetic is integer only and part of the contract (tests/_warp_ref.py restates
+ * it in numpy), per output pixel (x, y):
+ *
+ *   sx = m0*x + m1*y + m2,  sy = m3*x + m4*y + m5        (int64, Q16)
+ *   BILINEAR  qx = (sx + 128) >> 8 (arithmetic shift: floor), ix = qx >> 8,
+ *             fx = qx & 255; the same for y; per channel
+ *               top = p00*(256-fx) + p01*fx,  bot = p10*(256-fx) + p11*fx
+ *               out = (top*(256-fy) + bot*fy + 32768) >> 16
+ *             with p00 = src[iy][ix], p01 = src[iy][ix+1], p10 = src[iy+1][ix],
+ *             p11 = src[iy+1][ix+1]  (fx = fy = 0 returns p00 exactly)
+ *   NEAREST   ix = (sx + 32768) >> 16, iy likewise, out = src[iy][ix]
+ *
+ * ix and iy are clamped into [-2, dim + 1] first (no visible effect in CONSTANT
+ * and REPLICATE mode; in REFLECT101 mode the image does not repeat further out),
+ * then every tap index (ix, ix+1, iy, iy+1) goes through the border rule on its
+ * own; the kernel forms addresses from in-range indices only. */
+#define HKP_WARP_BILINEAR 0
+#define HKP_WARP_NEAREST  1
+#define HKP_WARP_BORDER_CONSTANT   0   /* a tap outside the source takes fill[c] (each tap on its own) */
+#define HKP_WARP_BORDER_REPLICATE  1   /* tap indices clamped */
+#define HKP_WARP_BORDER_REFLECT101 2   /* tap indices reflected without repeating the edge (-1 -> 1, dim -> dim-2,
+                                          once, then clamped); hs, ws >= 2 */
+#define HKP_WARP_MAX_DIM 16384
+
+typedef struct hkp_warp_xform {   /* 32 bytes */
+    int32_t m[6];      /* inverse map, dest -> source, Q16: sx = m0*x + m1*y + m2, sy = m3*x + m4*y + m5 */
+    uint8_t fill[4];   /* B, G, R, unused */
+    int32_t reserved;  /* 0 */
+} hkp_warp_xform;
+
+/* One launch for the batch.  xforms_host and xforms hold the same n records: the
+ * host copy is validated here before anything is launched (device memory is not
+ * read), the device copy is what the kernel reads.  All dimensions in
+ * [1, HKP_WARP_MAX_DIM]; img_out must not overlap img_in.  Rows leave as dwords
+ * when w % 4 == 0 and img_out is 4-byte aligned, as bytes otherwise. */
+int hkp_warp_affine_u8(int32_t n, int32_t hs, int32_t ws, const uint8_t* img_in, int32_t h, int32_t w,
+                       uint8_t* img_out, const hkp_warp_xform* xforms_host, const hkp_warp_xform* xforms,
+                       int32_t interp, int32_t border, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
