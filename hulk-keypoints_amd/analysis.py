@@ -12,6 +12,12 @@ and the int32 (y, x) keypoints of all images are all-gathered; rank 0 saves
 them as preds/keypoints.npy ([n_images, K, 2], file order).  Images go through
 one at a time (batch 1, train-mode BN — analysis.py:36-42), so results do not
 depend on the GPU count.
+
+With config.RESIZE set, an image whose size differs from the model's is resampled
+on the GPU first (antialiased, hkp.resample.Resize(RESIZE, **RESIZE_PARAMS)); its
+row of keypoints.npy then holds the predictions mapped back into the source
+image's pixel coordinates (Resize's inverse label map, rounded to the nearest
+pixel), and the overlay is drawn on the resampled frame.
 """
 import os
 import sys
@@ -20,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from config import BACKBONE, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS
+from config import BACKBONE, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS
 from hkp import parallel
 from src.dataset import imread_bgr, transform
 from src.model import KeypointsGauss
@@ -51,10 +57,20 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
     for i in range(lo, hi):
         img = imread_bgr(os.path.join(image_dir, files[i]))
         print(img.shape)
+        plan = None
+        if RESIZE is not None and img.shape[:2] != (IMG_HEIGHT, IMG_WIDTH):
+            from hkp import ops
+            from hkp.resample import Resize
+            plan = Resize(filter=RESIZE, **RESIZE_PARAMS).plan([img.shape[:2]], (IMG_HEIGHT, IMG_WIDTH))
+            flat = torch.from_numpy(np.ascontiguousarray(img).reshape(-1)).cuda()
+            img = ops.resample_ragged_u8(flat, plan)[0].cpu().numpy()
         img_t = transform(img).cuda()
         with torch.no_grad():
             heatmap, kp = keypoints.heatmaps_and_keypoints(img_t.view(-1, *img_t.shape))
         prediction.plot(img, heatmap.cpu().numpy(), image_id=i, keypoints=kp.cpu().numpy(), out_dir=out_dir)
+        if plan is not None:                         # (y, x) on the resampled frame -> the source image's pixels
+            uv = plan.invert_uv(kp[:1].cpu().numpy()[..., ::-1].astype(np.float32))
+            kp = torch.from_numpy(np.rint(uv[..., ::-1]).astype(np.int32)).to(kp.device)
         kps.append(kp[0])
     local_kp = torch.stack(kps) if kps else torch.zeros((0, NUM_KEYPOINTS, 2), dtype=torch.int32, device="cuda")
     all_kp = parallel.gather_keypoints(local_kp).cpu().numpy()

@@ -6,7 +6,12 @@ DOMAIN_RANDOMIZATION (True: the train set goes through the reference's commented
 augmentation pipeline, dataset.py:18-31, on the GPU) and DR_SEED (its seed),
 GEOMETRIC_AUGMENTATION (True: the train set's images and labels go through
 hkp.geometry.GeometricAugmentation — rotation, scale, translation, flips; not in the
-reference), GA_SEED (its seed) and GA_PARAMS (its other keyword arguments).
+reference), GA_SEED (its seed) and GA_PARAMS (its other keyword arguments),
+RESIZE (None: every image file already has IMG_WIDTH x IMG_HEIGHT, as the reference
+assumes; a filter name — "box", "bilinear", "hamming", "bicubic", "lanczos" — : files
+of any size are resampled on the GPU to that size, antialiased, hkp.resample.Resize,
+with the labels in each file's own pixel coordinates) and RESIZE_PARAMS (its other
+keyword arguments: mode="stretch" / "fit", fill=(B, G, R)).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -22,3 +27,5 @@ DR_SEED = 0
 GEOMETRIC_AUGMENTATION = False
 GA_SEED = 0
 GA_PARAMS = {}
+RESIZE = None
+RESIZE_PARAMS = {}

@@ -4,5 +4,6 @@ _lib      ctypes binding of libhulkkp.so (include/hulkkp.h)
 ops       tensor-level kernel wrappers
 net       network executor over the reference-shaped module tree
 autograd  the autograd.Function that runs the backward kernels
+resample  antialiased resize of uint8 images of any size (axis tables, plans, label maps)
 """
 from ._lib import HkpError, LIB_PATH, lib, version  # noqa: F401

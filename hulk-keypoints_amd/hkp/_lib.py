@@ -86,6 +86,19 @@ class WarpXform(ctypes.Structure):
 
 assert ctypes.sizeof(WarpXform) == 32
 
+
+class ResampleImage(ctypes.Structure):
+    """hkp_resample_image (hkp_resample_u8): where one image of the batch lies in the
+    flat input, its size, the word offsets of its axis tables, its destination
+    rectangle and the fill colour (B, G, R, unused)."""
+    _fields_ = [("offset", ctypes.c_int64), ("hs", ctypes.c_int32), ("ws", ctypes.c_int32),
+                ("xtab", ctypes.c_int64), ("ytab", ctypes.c_int64), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32),
+                ("wd", ctypes.c_int32), ("hd", ctypes.c_int32), ("fill", ctypes.c_uint8 * 4),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+assert ctypes.sizeof(ResampleImage) == 64
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -183,6 +196,9 @@ SIGNATURES = {
     # affine warp (xforms_host: WarpXform array on the host, xforms: its device copy)
     "hkp_warp_affine_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(WarpXform), _P, _I32,
                                           _I32, _P]),
+    # antialiased resize (records_host / tables_host: host copies, validated; records / tables: device copies)
+    "hkp_resample_u8": (ctypes.c_int, [_I32, _P, _I64, ctypes.POINTER(ResampleImage), _P, _P, _P, _I64, _I32, _I32,
+                                       _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

@@ -593,6 +593,42 @@ def resize_u8(img, h, w, interp="bilinear"):
     return warp_affine_u8(img, plan)
 
 
+def resample_ragged_u8(flat, plan):
+    """Antialiased resize (csrc/resample.hip) of a batch of images of different
+    sizes: flat uint8 [plan.in_bytes] on the device, the images of plan.sizes packed
+    one after the other, and the batch's hkp.resample.ResamplePlan → uint8
+    [B,h,w,3] with (h, w) = plan.hw; one launch on the current stream, bit for bit
+    Pillow's Image.resize(..., reducing_gap=None).  The plan's records and tables
+    are uploaded on that stream."""
+    _need(flat, torch.uint8, "resample_ragged_u8.flat", 1)
+    n = getattr(plan, "n", None)
+    if n is None or n < 1:
+        raise HkpError("resample_ragged_u8: expected a ResamplePlan, got %s" % type(plan).__name__)
+    if flat.numel() != plan.in_bytes:
+        raise HkpError("resample_ragged_u8: the plan's %d images take %d bytes, the buffer has %d"
+                       % (n, plan.in_bytes, flat.numel()))
+    h, w = plan.hw
+    recs, tables = plan.device_arrays(flat.device)
+    out = torch.empty((n, h, w, 3), device=flat.device, dtype=torch.uint8)
+    call("hkp_resample_u8", n, _ptr(flat), plan.in_bytes, plan.records, _ptr(recs),
+         ctypes.c_void_p(plan.tables.ctypes.data), _ptr(tables), plan.tables.size, h, w, _ptr(out), _stream())
+    return out
+
+
+def resample_u8(img, h, w, filter="bilinear", mode="stretch", fill=(0, 0, 0)):
+    """img uint8 [B,Hs,Ws,3] → [B,h,w,3], antialiased: Pillow's Image.resize((w, h),
+    filter, reducing_gap=None) bit for bit.  filter: "box", "bilinear", "hamming",
+    "bicubic", "lanczos"; mode "stretch", or "fit" (aspect ratio kept, the rest
+    filled with `fill`, (B, G, R))."""
+    from . import resample
+    _need(img, torch.uint8, "resample_u8.img", 4)
+    n, hs, ws, c = img.shape
+    if c != 3 or n < 1 or hs < 1 or ws < 1:
+        raise HkpError("resample_u8: img must be a non-empty [B,H,W,3], got %s" % (tuple(img.shape),))
+    plan = resample.ResamplePlan([(hs, ws)] * n, (h, w), filter=filter, mode=mode, fill=fill)
+    return resample_ragged_u8(img.reshape(-1), plan)
+
+
 def heat_overlay(heat, img, yx):
     """Prediction.plot's picture on the GPU: heat [B,K,H,W] fp32,
     img uint8 [B,H,W,3] BGR, yx int32 [B,K,2] argmax → uint8 [B, H*K/2, 2W, 3]

@@ -102,12 +102,19 @@ def vis_gauss(gaussians):
 
 class KeypointsDataset(Dataset):
     def __init__(self, img_folder, labels_folder, num_keypoints, img_height, img_width, transform, gauss_sigma=8,
-                 return_uv=False, device="cuda", geometric=None):
+                 return_uv=False, device="cuda", geometric=None, resize=None):
         """geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, the decoded
         uint8 image and the host label go through it (on the GPU: keep num_workers=0)
         before `transform`, under the sample's own index and the epoch of set_epoch();
-        the returned uv / Gaussians come from the transformed label."""
+        the returned uv / Gaussians come from the transformed label.
+
+        resize: a hkp.resample.Resize, or None.  When set, the image files may have any
+        size: the stored labels stay in each file's own pixel coordinates (not clipped
+        at load), and every decoded image is resampled on the GPU (antialiased,
+        hkp_resample_u8; keep num_workers=0) to (img_height, img_width) before
+        `geometric`, its label mapped by the same transform and then clipped."""
         self.geometric = geometric
+        self.resize = resize
         self.epoch = 0
         self.device = device
         self.num_keypoints = num_keypoints
@@ -121,8 +128,9 @@ class KeypointsDataset(Dataset):
         self.labels_np = []           # host copies (DataLoader workers never touch the device)
         for i in range(len(os.listdir(labels_folder))):
             label = np.load(os.path.join(labels_folder, "%05d.npy" % i)).reshape(num_keypoints, 2)
-            label[:, 0] = np.clip(label[:, 0], 0, self.img_width - 1)      # dataset.py:65
-            label[:, 1] = np.clip(label[:, 1], 0, self.img_height - 1)     # dataset.py:66
+            if resize is None:
+                label[:, 0] = np.clip(label[:, 0], 0, self.img_width - 1)      # dataset.py:65
+                label[:, 1] = np.clip(label[:, 1], 0, self.img_height - 1)     # dataset.py:66
             self.imgs.append(os.path.join(img_folder, "%05d.jpg" % i))
             self.labels.append(torch.from_numpy(label).to(device))
             self.labels_np.append(label.astype(np.float32))
@@ -134,9 +142,16 @@ class KeypointsDataset(Dataset):
     def _decode(self, index):
         """(uint8 HWC image, [K,2] labels on the device), through `geometric` when set."""
         img = imread_bgr(self.imgs[index])
-        if self.geometric is None:
+        if self.geometric is None and self.resize is None:
             return img, self.labels[index]
-        img, uv = self.geometric(img, self.labels_np[index], index=index, epoch=self.epoch)
+        uv = self.labels_np[index]
+        if self.resize is not None:
+            plan = self.resize.plan([img.shape[:2]], (self.img_height, self.img_width))
+            flat = torch.from_numpy(np.ascontiguousarray(img).reshape(-1)).to(self.device)
+            img = ops.resample_ragged_u8(flat, plan)[0].cpu().numpy()
+            uv = plan.apply_uv(uv[None])[0]
+        if self.geometric is not None:
+            img, uv = self.geometric(img, uv, index=index, epoch=self.epoch)
         return img, torch.from_numpy(uv).to(self.device)
 
     def __getitem__(self, index):
@@ -215,6 +230,33 @@ def _collate_coef(items):
     return ("img", torch.from_numpy(np.stack(imgs)), uv)
 
 
+def _collate_ragged(items):
+    """One batch of _RawView items whose images may differ in size: ("ragged", flat
+    uint8 [sum of H*W*3] with the images packed one after the other, int64 [B,2]
+    (H, W) sizes, uv) — no np.stack."""
+    imgs = [np.ascontiguousarray(it[0]) for it in items]
+    sizes = np.array([im.shape[:2] for im in imgs], dtype=np.int64).reshape(-1, 2)
+    flat = np.empty(int(sum(im.size for im in imgs)), dtype=np.uint8)
+    off = 0
+    for im in imgs:
+        flat[off:off + im.size] = im.reshape(-1)
+        off += im.size
+    uv = torch.from_numpy(np.stack([it[1] for it in items]))
+    return ("ragged", torch.from_numpy(flat), torch.from_numpy(sizes), uv)
+
+
+def _collate_coef_ragged(items):
+    """_collate_coef for DeviceBatches(resize=...): the "coef" batch when every image
+    went through the entropy decoder with one geometry, else the host decode packed
+    by _collate_ragged (the images may differ in size)."""
+    from hkp import jpeg
+    if all(it[0] == "coef" for it in items):
+        g0 = jpeg.Geom.from_buffer_copy(items[0][1][2]).key()
+        if all(jpeg.Geom.from_buffer_copy(it[1][2]).key() == g0 for it in items):
+            return _collate_coef(items)
+    return _collate_ragged([(it[1] if it[0] == "img" else imread_bgr(it[3]), it[2]) for it in items])
+
+
 class _EpochBatches:
     """Batch sampler of the persistent decode loader: the current epoch's index
     batches (set by DeviceBatches before each epoch; iterated in the main process)."""
@@ -267,10 +309,20 @@ class DeviceBatches:
     its stored label), and the labels that are uploaded are plan.apply_uv(uv): moved
     by the same transform, flip pairs exchanged, clipped to the image.  The
     dataset's own `geometric` is not applied here (the decode workers read the raw
-    files)."""
+    files).
+
+    resize: a hkp.resample.Resize, or None.  When set, the image files may have any
+    size, also inside one batch: the decode workers hand the images over packed in
+    one flat pinned buffer with their sizes, and the batch is resampled (antialiased,
+    hkp_resample_u8, one launch) to the dataset's (img_height, img_width) on the copy
+    stream right after its copy / JPEG reconstruct, before `geometric` and `augment`;
+    the labels that go on are plan.apply_uv(uv).  Build the dataset with the same
+    `resize`, so that its stored labels are in each file's own pixel coordinates.
+    With decode="device" a batch of one JPEG geometry is reconstructed on the device
+    and then resampled; a batch of mixed geometry takes the host decode."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, drop_last=False, device="cuda", workers=0,
-                 prefetch=4, decode="host", augment=None, geometric=None):
+                 prefetch=4, decode="host", augment=None, geometric=None, resize=None):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
         self.ds, self.bs, self.shuffle, self.seed, self.drop_last = dataset, batch_size, shuffle, seed, drop_last
@@ -278,6 +330,7 @@ class DeviceBatches:
         self.workers, self.prefetch, self.decode = workers, prefetch, decode
         self.augment = augment
         self.geometric = geometric
+        self.resize = resize
         self.epoch = 0
         self._loader = None
         self._sampler = _EpochBatches()
@@ -286,11 +339,17 @@ class DeviceBatches:
         n = len(self.ds)
         return n // self.bs if self.drop_last else (n + self.bs - 1) // self.bs
 
+    def _view_collate(self):
+        """The decode workers' dataset view and collate function."""
+        if self.resize is not None:
+            return ((_RawView(self.ds), _collate_ragged) if self.decode == "host"
+                    else (_CoefView(self.ds), _collate_coef_ragged))
+        return ((_RawView(self.ds), _collate_u8) if self.decode == "host" else (_CoefView(self.ds), _collate_coef))
+
     def _host_batches(self, batches):
         """Per index batch, in order: ("img", pinned uint8 [B,H,W,3], float32 [B,K,2])
         or (decode="device") ("coef", pinned coefs, pinned qt, geometry bytes, uv)."""
-        view, collate = ((_RawView(self.ds), _collate_u8) if self.decode == "host"
-                         else (_CoefView(self.ds), _collate_coef))
+        view, collate = self._view_collate()
         if self.workers <= 0:
             for idx in batches:
                 yield self._tag(collate([view[i] for i in idx]))
@@ -306,6 +365,8 @@ class DeviceBatches:
 
     def _tag(self, b):
         """Host batches in one form, tensors pinned (the loader pins them already)."""
+        if self.resize is not None:            # ("ragged", flat, sizes, uv) or ("coef", ...)
+            return tuple(t.pin_memory() if torch.is_tensor(t) and not t.is_pinned() else t for t in b)
         if self.decode == "host":
             imgs, uv = b
             return ("img", imgs if imgs.is_pinned() else imgs.pin_memory(), uv)
@@ -329,7 +390,11 @@ class DeviceBatches:
             b = next(host)
             idx = next(staged)
             with torch.cuda.stream(copy_stream):
-                if b[0] == "img":
+                rsizes = None
+                if b[0] == "ragged":           # images of any size, packed: resampled below
+                    buf, rsizes, uv = b[1], b[2].numpy(), b[3]
+                    img = buf.to(self.device, non_blocking=True)
+                elif b[0] == "img":
                     buf, uv = b[1], b[2]
                     img = buf.to(self.device, non_blocking=True)
                 else:                          # hybrid decode: coefficients up, pixels made on the device
@@ -339,6 +404,13 @@ class DeviceBatches:
                     g = jpeg.Geom.from_buffer_copy(gbytes)
                     img = jpeg.reconstruct(coefs.to(self.device, non_blocking=True),
                                            qt.to(self.device, non_blocking=True), g, coefs.shape[0])
+                if self.resize is not None:
+                    if rsizes is None:         # a reconstructed batch: one size
+                        rsizes = [(img.shape[1], img.shape[2])] * img.shape[0]
+                    rplan = self.resize.plan(rsizes, (self.ds.img_height, self.ds.img_width))
+                    img = ops.resample_ragged_u8(img.reshape(-1), rplan)
+                    uv = rplan.apply_uv(uv).pin_memory()
+                    buf = (buf, rplan, uv)     # the plan's pinned records and tables live as long as the batch's
                 if self.geometric is not None:
                     gplan = self.geometric.plan(idx, epoch, uvs=uv, hw=(img.shape[1], img.shape[2]))
                     img = ops.warp_affine_u8(img, gplan)

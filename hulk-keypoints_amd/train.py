@@ -22,7 +22,7 @@ from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
 from config import (BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GA_PARAMS, GA_SEED, GAUSS_SIGMA, GEOMETRIC_AUGMENTATION,
-                    IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS, batch_size, epochs)
+                    IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp.train import GradBucketer, broadcast_state
 from src.dataset import KeypointsDataset, domain_randomization, transform
@@ -117,12 +117,16 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
     if GEOMETRIC_AUGMENTATION:                      # images and labels together; the train set only
         from hkp.geometry import GeometricAugmentation
         geometric = GeometricAugmentation(seed=GA_SEED, **GA_PARAMS)
+    resize = None
+    if RESIZE is not None:                          # image files of any size; train and test set alike
+        from hkp.resample import Resize
+        resize = Resize(filter=RESIZE, **RESIZE_PARAMS)
     train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir, "data/%s/train/keypoints" % dataset_dir,
                                      NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA,
-                                     return_uv=True, geometric=geometric)
+                                     return_uv=True, geometric=geometric, resize=resize)
     test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
-                                    return_uv=True)
+                                    return_uv=True, resize=resize)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset) if world > 1 else None
     train_data = DataLoader(train_dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
                             num_workers=workers)

@@ -778,6 +778,62 @@ int hkp_warp_affine_u8(int32_t n, int32_t hs, int32_t ws, const uint8_t* img_in,
                        uint8_t* img_out, const hkp_warp_xform* xforms_host, const hkp_warp_xform* xforms,
                        int32_t interp, int32_t border, hkp_stream_t stream);
 
+/* ------------------------------------------------- antialiased resize ---- */
+/* Batched antialiased resize of uint8 BGR images of ANY size (each image of the
+ * batch has its own) into uint8 [n][h][w][3]: the first stage of the data path,
+ * decoded frame -> network-size frame.  The result equals Pillow's
+ * Image.resize((wd, hd), filter, reducing_gap=None) of an RGB image bit for bit
+ * (tests/_resample_ref.py restates it in numpy; tests pin both).  The resampler is
+ * separable, horizontal pass first; the filter lives in host-built axis tables
+ * (hkp/resample.py) and the device arithmetic is integer only.  Per image, with
+ * its x table (ws -> wd) and its y table (hs -> hd), for every pixel (xx, yy) of
+ * the destination rectangle and every channel:
+ *
+ *   mid[sy][xx] = clip((2^21 + sum_{t < xcnt[xx]} src[sy][xmin[xx] + t] * kx[xx][t]) >> 22, 0, 255)
+ *   out[y0 + yy][x0 + xx] = clip((2^21 + sum_{t < ycnt[yy]} mid[ymin[yy] + t][xx] * ky[yy][t]) >> 22, 0, 255)
+ *
+ * (>> is an arithmetic shift; int32 accumulators suffice: the coefficients of a
+ * row sum to 2^22 and the negative lobes of the filters fit the two spare bits).
+ * mid is Pillow's uint8 intermediate image; the kernel keeps it in registers, one
+ * pixel at a time, and never writes it to memory.  An axis that keeps its size
+ * takes the identity table (cnt = 1, k = 2^22), which returns the pixel exactly.
+ * Output pixels outside the destination rectangle take the fill colour.
+ *
+ * Axis table, int32 words at a word offset into `tables`:
+ *   [0] ksize   [1] out   then out x (xmin, cnt)   then out x ksize coefficients
+ * (row xx's coefficients start at word 2 + 2*out + xx*ksize; cnt of them are read).
+ * Built on the host in float64 as Pillow builds them: scale = in/out,
+ * fs = max(scale, 1), support = filter_support * fs, ksize = ceil(support)*2 + 1,
+ * center = (xx + 0.5)*scale, xmin = max(int(center - support + 0.5), 0),
+ * cnt = min(int(center + support + 0.5), in) - xmin,
+ * w[t] = filter((t + xmin - center + 0.5) * (1/fs)), divided by their sum (index
+ * order) unless it is 0, k[t] = int(w*2^22 + 0.5) (w >= 0) or int(w*2^22 - 0.5)
+ * (w < 0), both truncating. */
+typedef struct hkp_resample_image {   /* 64 bytes */
+    int64_t offset;      /* byte offset of the image (uint8 [hs][ws][3]) inside img_in */
+    int32_t hs, ws;      /* source size                                                */
+    int64_t xtab, ytab;  /* word offsets of the x (ws -> wd) and y (hs -> hd) tables   */
+    int32_t x0, y0;      /* destination rectangle inside the h x w output ...          */
+    int32_t wd, hd;      /* ... and its size                                           */
+    uint8_t fill[4];     /* B, G, R, unused: the colour outside the rectangle          */
+    int32_t reserved[3]; /* 0 */
+} hkp_resample_image;
+
+/* One launch for the batch, no workspace.  records_host / records hold the same n
+ * records and tables_host / tables the same table_words int32 words: the host
+ * copies are validated here before anything is launched (device memory is not
+ * read), the device copies are what the kernel reads.  Checked: every image lies
+ * inside in_bytes; table offsets and sizes lie inside table_words; a table's `out`
+ * equals wd / hd; xmin >= 0, cnt >= 0, xmin + cnt <= the source extent and
+ * cnt <= ksize for every output index; the rectangle lies inside h x w; all
+ * dimensions in [1, HKP_WARP_MAX_DIM]; reserved == 0; img_out does not overlap
+ * img_in.  Coefficients are not checked (they cannot form an address).  Rows
+ * leave as dwords when w % 4 == 0 and img_out is 4-byte aligned, as bytes
+ * otherwise. */
+int hkp_resample_u8(int32_t n, const uint8_t* img_in, int64_t in_bytes, const hkp_resample_image* records_host,
+                    const hkp_resample_image* records, const int32_t* tables_host, const int32_t* tables,
+                    int64_t table_words, int32_t h, int32_t w, uint8_t* img_out, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
