@@ -18,6 +18,14 @@ on the GPU first (antialiased, hkp.resample.Resize(RESIZE, **RESIZE_PARAMS)); it
 row of keypoints.npy then holds the predictions mapped back into the source
 image's pixel coordinates (Resize's inverse label map, rounded to the nearest
 pixel), and the overlay is drawn on the resampled frame.
+
+With config.PEAKS set (a dict of KeypointsGauss.predict_peaks's keyword arguments)
+the same forward's low-res logits also go through the multi-peak decode
+(ops.heat_peaks): rank 0 saves preds/peaks.npy (float32 [n_images, K, max_peaks, 3]:
+(x, y, score) per local maximum, sub-pixel, best first, unused slots (-1, -1, 0); with
+RESIZE in each source image's pixels, unrounded) and preds/peak_counts.npy (int32
+[n_images, K]), file order, all-gathered like the keypoints.  keypoints.npy and the
+overlays are what they are without it.
 """
 import os
 import sys
@@ -26,8 +34,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from config import BACKBONE, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS
-from hkp import parallel
+from config import BACKBONE, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS, PEAKS, RESIZE, RESIZE_PARAMS
+from hkp import net, ops, parallel
 from src.dataset import imread_bgr, transform
 from src.model import KeypointsGauss
 from src.prediction import Prediction
@@ -53,20 +61,29 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
     prediction = Prediction(keypoints, NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, use_cuda)
     files = sorted(os.listdir(image_dir))
     lo, hi = parallel.shard_range(len(files), parallel.rank(), parallel.world())
-    kps = []
+    kps, pks, cts = [], [], []
+    npk = int(PEAKS.get("max_peaks", 4)) if PEAKS is not None else 0
     for i in range(lo, hi):
         img = imread_bgr(os.path.join(image_dir, files[i]))
         print(img.shape)
         plan = None
         if RESIZE is not None and img.shape[:2] != (IMG_HEIGHT, IMG_WIDTH):
-            from hkp import ops
             from hkp.resample import Resize
             plan = Resize(filter=RESIZE, **RESIZE_PARAMS).plan([img.shape[:2]], (IMG_HEIGHT, IMG_WIDTH))
             flat = torch.from_numpy(np.ascontiguousarray(img).reshape(-1)).cuda()
             img = ops.resample_ragged_u8(flat, plan)[0].cpu().numpy()
         img_t = transform(img).cuda()
         with torch.no_grad():
-            heatmap, kp = keypoints.heatmaps_and_keypoints(img_t.view(-1, *img_t.shape))
+            if PEAKS is None:
+                heatmap, kp = keypoints.heatmaps_and_keypoints(img_t.view(-1, *img_t.shape))
+            else:                                    # the same forward; its low-res logits feed the peak decode
+                heatmap, kp, low = net.keypoints_forward(keypoints.resnet.net, img_t.view(-1, *img_t.shape),
+                                                         NUM_KEYPOINTS, heat=True, argmax=True, pol=keypoints.policy)
+                pk, ct = ops.heat_peaks(low, IMG_HEIGHT, IMG_WIDTH, **PEAKS)
+                if plan is not None:                 # (x, y) of the used slots -> the source image's pixels
+                    pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
+                pks.append(pk[0])
+                cts.append(ct[0])
         prediction.plot(img, heatmap.cpu().numpy(), image_id=i, keypoints=kp.cpu().numpy(), out_dir=out_dir)
         if plan is not None:                         # (y, x) on the resampled frame -> the source image's pixels
             uv = plan.invert_uv(kp[:1].cpu().numpy()[..., ::-1].astype(np.float32))
@@ -74,9 +91,17 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
         kps.append(kp[0])
     local_kp = torch.stack(kps) if kps else torch.zeros((0, NUM_KEYPOINTS, 2), dtype=torch.int32, device="cuda")
     all_kp = parallel.gather_keypoints(local_kp).cpu().numpy()
+    if PEAKS is not None:
+        local_pk = torch.stack(pks) if pks else torch.zeros((0, NUM_KEYPOINTS, npk, 3), dtype=torch.float32,
+                                                            device="cuda")
+        local_ct = torch.stack(cts) if cts else torch.zeros((0, NUM_KEYPOINTS), dtype=torch.int32, device="cuda")
+        all_pk, all_ct = (t.cpu().numpy() for t in parallel.gather_peaks(local_pk, local_ct))
     if parallel.rank() == 0:
         os.makedirs(out_dir, exist_ok=True)
         np.save(os.path.join(out_dir, "keypoints.npy"), all_kp)
+        if PEAKS is not None:
+            np.save(os.path.join(out_dir, "peaks.npy"), all_pk)
+            np.save(os.path.join(out_dir, "peak_counts.npy"), all_ct)
     if own_group:
         dist.destroy_process_group()
     return all_kp

@@ -11,7 +11,13 @@ RESIZE (None: every image file already has IMG_WIDTH x IMG_HEIGHT, as the refere
 assumes; a filter name — "box", "bilinear", "hamming", "bicubic", "lanczos" — : files
 of any size are resampled on the GPU to that size, antialiased, hkp.resample.Resize,
 with the labels in each file's own pixel coordinates) and RESIZE_PARAMS (its other
-keyword arguments: mode="stretch" / "fit", fill=(B, G, R)).
+keyword arguments: mode="stretch" / "fit", fill=(B, G, R)), PEAKS (None: analysis.py
+writes what the reference writes; a dict of KeypointsGauss.predict_peaks's keyword
+arguments, e.g. {"max_peaks": 4, "radius": 1, "threshold": 0.1}: analysis.py also
+writes preds/peaks.npy — float32 [n_images, K, max_peaks, 3], (x, y, score) per local
+maximum of each heatmap, sub-pixel, best first, unused slots (-1, -1, 0), in each
+source image's pixels when RESIZE is set — and preds/peak_counts.npy, int32
+[n_images, K]; keypoints.npy and the overlays do not change).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -29,3 +35,4 @@ GA_SEED = 0
 GA_PARAMS = {}
 RESIZE = None
 RESIZE_PARAMS = {}
+PEAKS = None

@@ -438,6 +438,172 @@ __global__ __launch_bounds__(256) void gauss_target_kernel(int K, int H, int W, 
     }
 }
 
+// ---- hkp_heat_peaks: local maxima of the low-res logits, top P per plane, each
+// with a score and a sub-lattice position (include/hulkkp.h has the definition).
+//
+// One 1024-thread block per (n,k) plane, the plane staged in LDS (NaN -> -inf,
+// -0 -> +0, so plain float compares are the definition's order).  Thread t owns
+// nodes t, t + 1024, ... (at most 32: the plane cap) and runs the window test on
+// each: a window row at a time, nearest rows first, the row's 2 RMAX + 1 LDS
+// reads issued together (RMAX = 2 or 8: the compiled half-width; columns outside
+// the radius or the plane are masked) and folded into the maxima left of, at and
+// right of the node's column — "beats" is >= for the nodes of smaller index and
+// > for the others — leaving after the first row that holds a winner.  (With 256
+// threads, each wave alone on its SIMD, and one compare chain per neighbour the
+// radius-8 test ran at the latency of its dependent instructions, 3.7-4.2x as
+// long: DESIGN "Multi-peak decode".)  The thread keeps its candidates as a
+// bit mask in a register and the best of them as a 64-bit key (ordered logit bits
+// | inverted index: unique, so max is the definition's order and ties never depend
+// on arrival).  Selection is up to P rounds of a fixed-order block max (wave
+// shuffles, one LDS hand-off per round, double-buffered); the owner of the
+// winning key retires that bit and rebuilds its best from its mask.  Lanes 0..P-1
+// then refine one peak each in fp64.  No atomics; every index that forms an
+// address is < h*w by construction and clamped once more where it comes back
+// from LDS.
+constexpr int PEAKS_THREADS = 1024;
+constexpr int PEAKS_WAVES = PEAKS_THREADS / 64;
+constexpr int PEAKS_CAP = PEAKS_THREADS * 32;              // 32768 nodes = 128 KiB of LDS
+constexpr int PEAKS_MAX = 16;
+
+__device__ __forceinline__ unsigned long long peak_key(float z, unsigned idx) {
+    // z is no NaN and no -0: these bits order like the values
+    const unsigned b = __float_as_uint(z);
+    const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+}
+
+// log sigmoid(z) in fp64: -d^2 / 2 sigma^2 for the Gaussian target
+__device__ __forceinline__ double log_sigmoid_d(float zf) {
+    const double z = (double)zf;
+    return fmin(z, 0.0) - log1p(exp(-fabs(z)));
+}
+
+// vertex offset of the parabola through (-1, gm), (0, g0), (1, gp), in [-0.5, 0.5]
+__device__ __forceinline__ double peak_offset(double gm, double g0, double gp) {
+    if (!(isfinite(gm) && isfinite(g0) && isfinite(gp))) return 0.0;
+    const double den = 2.0 * g0 - gm - gp;
+    if (!(den > 1e-6)) return 0.0;
+    const double d = 0.5 * (gp - gm) / den;
+    return fmin(fmax(d, -0.5), 0.5);
+}
+
+template <int CAP, bool VEC4, int RMAX>
+__global__ __launch_bounds__(PEAKS_THREADS) void heat_peaks_kernel(int h, int w, int H, int W, int radius, int P,
+                                                                  float thr, const float* __restrict__ low,
+                                                                  float* __restrict__ peaks, int* __restrict__ counts) {
+    __shared__ __attribute__((aligned(16))) float pz[CAP];
+    __shared__ unsigned long long wkey[2][PEAKS_WAVES];
+    __shared__ unsigned sel[PEAKS_MAX];
+    const int tid = threadIdx.x;
+    const int hw = h * w;                                   // <= CAP (host-checked)
+    const size_t plane = blockIdx.x;
+    const float* x = low + plane * (size_t)hw;
+    if constexpr (VEC4) {                                   // hw % 4 == 0 and a 16-byte aligned base
+        for (int i = tid * 4; i < hw; i += 4 * PEAKS_THREADS) {
+            f32x4 v = *(const f32x4*)(x + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] != v[e] ? -INFINITY : (v[e] == 0.f ? 0.f : v[e]);
+            *(f32x4*)(pz + i) = v;
+        }
+    } else {
+        for (int i = tid; i < hw; i += PEAKS_THREADS) {
+            const float v = x[i];
+            pz[i] = v != v ? -INFINITY : (v == 0.f ? 0.f : v);
+        }
+    }
+    __syncthreads();
+
+    unsigned mask = 0u;                                     // bit b: node tid + 1024 b is a candidate
+    unsigned long long mine = 0ull;
+    for (int bit = 0; bit < 32; ++bit) {
+        const int i = tid + PEAKS_THREADS * bit;
+        if (i >= hw) break;
+        const float za = pz[i];
+        bool c = za > -INFINITY;
+        if (c) {
+            const int yi = i / w, xj = i - yi * w;
+            for (int s = 0; s <= 2 * radius && c; ++s) {
+                const int dy = (s & 1) ? -((s + 1) >> 1) : (s >> 1);       // 0, -1, 1, -2, 2, ...
+                const int yy = yi + dy;
+                if (yy < 0 || yy >= h) continue;
+                const int row = yy * w;
+                float ml = -INFINITY, mr = -INFINITY;       // maxima left / right of the column (-inf never beats)
+#pragma unroll
+                for (int dx = 1; dx <= RMAX; ++dx) {
+                    const int xl = xj - dx, xr = xj + dx;
+                    const float zl = pz[row + max(xl, 0)], zr = pz[row + min(xr, w - 1)];
+                    ml = fmaxf(ml, (dx <= radius && xl >= 0) ? zl : -INFINITY);
+                    mr = fmaxf(mr, (dx <= radius && xr < w) ? zr : -INFINITY);
+                }
+                const float mc = pz[row + xj];
+                // smaller index: the rows above, and this row left of the node
+                const bool beaten = dy < 0 ? fmaxf(fmaxf(ml, mc), mr) >= za
+                                  : dy > 0 ? fmaxf(fmaxf(ml, mc), mr) > za
+                                           : (ml >= za || mr > za);
+                c = !beaten;
+            }
+            if (c) c = sigmoid_f(za) >= thr;
+        }
+        if (c) {
+            mask |= 1u << bit;
+            mine = umax64(mine, peak_key(za, (unsigned)i));
+        }
+    }
+
+    int cnt = 0;
+    for (; cnt < P; ++cnt) {
+        unsigned lo = (unsigned)mine, hi = (unsigned)(mine >> 32);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
+            const unsigned long long m = umax64(((unsigned long long)hi << 32) | lo, ((unsigned long long)oh << 32) | ol);
+            lo = (unsigned)m;
+            hi = (unsigned)(m >> 32);
+        }
+        unsigned long long* wk = wkey[cnt & 1];
+        if ((tid & 63) == 0) wk[tid >> 6] = ((unsigned long long)hi << 32) | lo;
+        __syncthreads();
+        unsigned long long best = wk[0];
+#pragma unroll
+        for (int v = 1; v < PEAKS_WAVES; ++v) best = umax64(best, wk[v]);
+        if (best == 0ull) break;                            // the same value in every thread
+        if (mine == best) {                                 // keys are unique: exactly one thread
+            const unsigned idx = 0xFFFFFFFFu - (unsigned)best;
+            sel[cnt] = idx;
+            mask &= ~(1u << (((idx - (unsigned)tid) / PEAKS_THREADS) & 31u));
+            mine = 0ull;
+            for (unsigned m = mask; m; m &= m - 1u) {
+                const int i = tid + PEAKS_THREADS * (__ffs(m) - 1);
+                if (i < hw) mine = umax64(mine, peak_key(pz[i], (unsigned)i));
+            }
+        }
+    }
+    __syncthreads();
+
+    if (tid == 0) counts[plane] = cnt;
+    if (tid < P) {
+        float* o = peaks + (plane * (size_t)P + (size_t)tid) * 3;
+        if (tid < cnt) {
+            const int i = min((int)sel[tid], hw - 1);
+            const int yi = i / w, xj = i - yi * w;
+            const float z0 = pz[i];
+            const double g0 = log_sigmoid_d(z0);
+            double dx = 0.0, dy = 0.0;
+            if (xj > 0 && xj < w - 1) dx = peak_offset(log_sigmoid_d(pz[i - 1]), g0, log_sigmoid_d(pz[i + 1]));
+            if (yi > 0 && yi < h - 1) dy = peak_offset(log_sigmoid_d(pz[i - w]), g0, log_sigmoid_d(pz[i + w]));
+            const double px = w > 1 ? ((double)xj + dx) * (double)(W - 1) / (double)(w - 1) : 0.0;
+            const double py = h > 1 ? ((double)yi + dy) * (double)(H - 1) / (double)(h - 1) : 0.0;
+            o[0] = (float)px;
+            o[1] = (float)py;
+            o[2] = sigmoid_f(z0);
+        } else {
+            o[0] = -1.f;
+            o[1] = -1.f;
+            o[2] = 0.f;
+        }
+    }
+}
+
 }  // namespace hkp
 
 using namespace hkp;
@@ -551,6 +717,40 @@ extern "C" int hkp_upsample_sigmoid(int32_t n, int32_t k, int32_t h, int32_t w, 
         hipLaunchKernelGGL(argmax_decode_kernel, dim3(nk), dim3(256), 0, st, (int)grid.x, W, keys, argmax_yx);
         HKP_LAUNCH_CHECK("hkp_upsample_sigmoid(decode)");
     }
+    return HKP_OK;
+}
+
+extern "C" int hkp_heat_peaks(int32_t n, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W, int32_t radius,
+                              int32_t max_peaks, float threshold, const float* lowres, float* peaks, int32_t* counts,
+                              hkp_stream_t stream) {
+    HKP_CHECK_ARG(n >= 1 && k >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1,
+                  "hkp_heat_peaks: bad sizes (n=%d k=%d h=%d w=%d H=%d W=%d)", n, k, h, w, H, W);
+    HKP_CHECK_ARG(radius >= 1 && radius <= 8, "hkp_heat_peaks: radius must be 1..8 (got %d)", radius);
+    HKP_CHECK_ARG(max_peaks >= 1 && max_peaks <= PEAKS_MAX, "hkp_heat_peaks: max_peaks must be 1..%d (got %d)",
+                  PEAKS_MAX, max_peaks);
+    HKP_CHECK_ARG(threshold >= 0.f && threshold <= 1.f, "hkp_heat_peaks: threshold must be in [0, 1] (got %g)",
+                  (double)threshold);
+    HKP_CHECK_ARG(lowres && peaks && counts, "hkp_heat_peaks: null tensor");
+    HKP_CHECK_ARG((long)h * w <= PEAKS_CAP, "hkp_heat_peaks: plane of %d x %d nodes exceeds the cap of %d (h*w)", h, w,
+                  PEAKS_CAP);
+    HKP_CHECK_ARG((long)n * k <= 0x7FFFFFFFL, "hkp_heat_peaks: too many planes");
+    const int hw = h * w;
+    const bool vec4 = (hw & 3) == 0 && ((uintptr_t)lowres & 15) == 0;
+    const dim3 grid((unsigned)(n * k));
+    hipStream_t st = as_stream(stream);
+#define HKP_PEAKS(CAP, V4, R)                                                                                 \
+    hipLaunchKernelGGL((heat_peaks_kernel<CAP, V4, R>), grid, dim3(PEAKS_THREADS), 0, st, h, w, H, W, radius, \
+                       max_peaks, threshold, lowres, peaks, counts)
+#define HKP_PEAKS_R(CAP, V4) \
+    if (radius <= 2) HKP_PEAKS(CAP, V4, 2); else HKP_PEAKS(CAP, V4, 8)
+    if (hw <= PEAKS_CAP / 4) {              // 32 KiB of LDS: several planes share a CU
+        if (vec4) { HKP_PEAKS_R(PEAKS_CAP / 4, true); } else { HKP_PEAKS_R(PEAKS_CAP / 4, false); }
+    } else {
+        if (vec4) { HKP_PEAKS_R(PEAKS_CAP, true); } else { HKP_PEAKS_R(PEAKS_CAP, false); }
+    }
+#undef HKP_PEAKS_R
+#undef HKP_PEAKS
+    HKP_LAUNCH_CHECK("hkp_heat_peaks");
     return HKP_OK;
 }
 

@@ -564,9 +564,10 @@ def fc_rows(resnet, k):
     return w.reshape(w.shape[0], -1)[:k], resnet.fc.bias[:k]
 
 
-def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, pol=None):
+def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, pol=None, upsample=True):
     """Fused K-channel head: heat = sigmoid(upsample(fc[:K](feat)))  (model.py:19-22).
-    pol: the execution policy (a trace carries its own)."""
+    pol: the execution policy (a trace carries its own).  upsample=False (the peak
+    decode, which reads `low` alone): no upsample launch, (None, None, low)."""
     pol = trace.policy if trace is not None else resolve(pol)
     if trace is not None and pol.precision in INFERENCE_ONLY:
         raise ops.HkpError("precision %r is inference-only; train with 'f16x3' or 'fp32'" % pol.precision)
@@ -576,6 +577,10 @@ def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, po
     else:
         feat = backbone_forward(resnet, x_nchw, trace, pol=pol)
         low = ops.head_fc(feat, w, b)
+    if not upsample:
+        if trace is not None:
+            raise ops.HkpError("keypoints_forward: a traced (training) forward needs the upsample")
+        return None, None, low
     H, W = image_nchw_shape(x_nchw)[2:]
     hm, yx = ops.upsample_sigmoid(low, H, W, heat=heat, argmax=argmax)
     if trace is not None:

@@ -660,6 +660,34 @@ def soft_argmax(heat, beta=1.0):
     return out
 
 
+HEAT_PEAKS_MAX_NODES = 32768          # PEAKS_CAP of csrc/head.hip: h * w of one plane
+
+
+def heat_peaks(low, H, W, max_peaks=4, radius=1, threshold=0.0):
+    """lowres logits [N,K,h,w] fp32 (what keypoints_forward returns as `low`) →
+    (peaks float32 [N,K,max_peaks,3], counts int32 [N,K]): per plane the up to
+    max_peaks best local maxima of its (2 radius + 1)^2 windows with
+    sigmoid(logit) >= threshold, best first, each as (x, y, score) — (x, y), the
+    order of soft_argmax and the labels, NOT the (y, x) of the argmax — with x, y
+    sub-lattice positions in pixels of the H x W output (align_corners frame) and
+    score the heatmap's value at the node.  Unused slots hold (-1, -1, 0).  The
+    definition is hkp_heat_peaks's (include/hulkkp.h); no heatmap is formed."""
+    _need(low, torch.float32, "heat_peaks.lowres", 4)
+    n, k, h, w = low.shape
+    if min(n, k, h, w) < 1 or h * w > HEAT_PEAKS_MAX_NODES:
+        raise HkpError("heat_peaks: lowres %s: need non-empty planes of at most %d nodes"
+                       % (tuple(low.shape), HEAT_PEAKS_MAX_NODES))
+    H, W, max_peaks, radius, threshold = int(H), int(W), int(max_peaks), int(radius), float(threshold)
+    if not 1 <= max_peaks <= 16 or not 1 <= radius <= 8 or not 0.0 <= threshold <= 1.0 or H < 1 or W < 1:
+        raise HkpError("heat_peaks: need 1 <= max_peaks <= 16, 1 <= radius <= 8, 0 <= threshold <= 1, H, W >= 1 "
+                       "(got max_peaks=%d radius=%d threshold=%g H=%d W=%d)" % (max_peaks, radius, threshold, H, W))
+    peaks = torch.empty((n, k, max_peaks, 3), device=low.device, dtype=torch.float32)
+    counts = torch.empty((n, k), device=low.device, dtype=torch.int32)
+    call("hkp_heat_peaks", n, k, h, w, H, W, radius, max_peaks, threshold, _ptr(low), _ptr(peaks), _ptr(counts),
+         _stream())
+    return peaks, counts
+
+
 # two-level finalize (hkp_bn_finalize_ws) from this many partial tiles on: C4 +2.2 %
 # (R50 C = 2048 convs, 4,800+ tiles); at 300-1,200 tiles (C2 layer2-4, the C3
 # shard) the one-kernel merge already fills the chip and its single launch won

@@ -53,6 +53,45 @@ def gather_keypoints(yx, group=None):
     return torch.cat([p[:c] for p, c in zip(parts, counts)])
 
 
+def _gather_ragged(parts_in, group):
+    """all_gather of several tensors sharing their first (shard) dimension, shards of
+    unequal size: one size exchange, each tensor padded to the largest shard for
+    its collective and trimmed after; rank order."""
+    n = dist.get_world_size(group)
+    b = parts_in[0].shape[0]
+    sizes = torch.tensor([b], device=parts_in[0].device, dtype=torch.int64)
+    all_sizes = [torch.empty_like(sizes) for _ in range(n)]
+    dist.all_gather(all_sizes, sizes, group=group)
+    shard = [int(s.item()) for s in all_sizes]
+    bmax = max(shard)
+    out = []
+    for t in parts_in:
+        t = t.contiguous()
+        if b < bmax:
+            t = torch.cat([t, torch.zeros((bmax - b,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)])
+        got = [torch.empty_like(t) for _ in range(n)]
+        dist.all_gather(got, t, group=group)
+        out.append(torch.cat([g[:c] for g, c in zip(got, shard)]))
+    return out
+
+
+def gather_peaks(peaks, counts, group=None):
+    """all_gather of each rank's multi-peak decode (ops.heat_peaks: peaks float32
+    [b_r, K, P, 3] (x, y, score), counts int32 [b_r, K]) → ([sum b_r, K, P, 3],
+    [sum b_r, K]) in rank order, on every rank.  Shards may differ in size, as for
+    gather_keypoints (which stays int32-only)."""
+    if peaks.dtype != torch.float32 or peaks.dim() != 4 or peaks.shape[3] != 3:
+        raise ValueError("gather_peaks: expected float32 [b, K, P, 3] peaks, got %s %s"
+                         % (peaks.dtype, tuple(peaks.shape)))
+    if counts.dtype != torch.int32 or tuple(counts.shape) != tuple(peaks.shape[:2]):
+        raise ValueError("gather_peaks: expected int32 %s counts, got %s %s"
+                         % (tuple(peaks.shape[:2]), counts.dtype, tuple(counts.shape)))
+    n = dist.get_world_size(group) if dist.is_initialized() else 1
+    if n == 1:
+        return peaks, counts
+    return tuple(_gather_ragged([peaks, counts], group))
+
+
 def gather_keypoints_fixed(yx, out=None, group=None):
     """gather_keypoints for equal shards (the bench's steady state): one
     all_gather_into_tensor, no size exchange; out: a [world*b, K, 2] int32 buffer
@@ -196,6 +235,20 @@ def predict_keypoints_dp(model, x_shard, heat=False, sync=False, group=None, glo
     else:
         hm, yx = None, model.predict_keypoints(x_shard, policy=pol)
     return gather_keypoints(yx, group), hm
+
+
+@torch.no_grad()
+def predict_peaks_dp(model, x_shard, max_peaks=4, radius=1, threshold=0.0, sync=False, group=None,
+                     global_batch=None):
+    """Each rank's shard through the fused forward and the multi-peak decode
+    (KeypointsGauss.predict_peaks); peaks and counts gathered.  sync / group /
+    global_batch: as for predict_keypoints_dp.
+    Returns (global float32 [B, K, max_peaks, 3] (x, y, score), global int32 [B, K])."""
+    pol = model.policy.with_(sync_bn=True, sync_group=group) if sync else model.policy
+    if sync:
+        ShardCheck(group)(x_shard.shape[0], global_batch)
+    peaks, counts = model.predict_peaks(x_shard, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=pol)
+    return gather_peaks(peaks, counts, group)
 
 
 # ---- SyncBN (SURVEY §8(e), caveat D5) ----------------------------------------

@@ -269,6 +269,23 @@ class ResamplePlan:
         out = ((a.astype(np.float64) - org + 0.5) / gain - 0.5).astype(np.float32)
         return torch.from_numpy(out) if is_t else out
 
+    def invert_peaks(self, peaks, counts):
+        """The multi-peak decode (ops.heat_peaks: peaks [n, K, P, 3] (x, y, score),
+        counts [n, K]; numpy or CPU tensors, the same kind comes back) mapped into
+        the source images' pixels: invert_uv on (x, y) of the first counts[b, k]
+        slots of every plane; the unused slots and the scores are left as they are."""
+        is_t = isinstance(peaks, torch.Tensor)
+        p = np.array(peaks.detach().cpu().numpy() if is_t else peaks, dtype=np.float32)      # a copy
+        c = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+        if p.ndim != 4 or p.shape[0] != self.n or p.shape[3] != 3 or c.shape != p.shape[:2]:
+            raise HkpError("invert_peaks: expected peaks [%d, K, P, 3] and counts [%d, K], got %s and %s"
+                           % (self.n, self.n, p.shape, c.shape))
+        n, k, pk, _ = p.shape
+        used = np.arange(pk)[None, None, :] < c[:, :, None]
+        xy = self.invert_uv(np.ascontiguousarray(p[..., :2]).reshape(n, k * pk, 2)).reshape(n, k, pk, 2)
+        p[..., :2] = np.where(used[..., None], xy, p[..., :2])
+        return torch.from_numpy(p) if is_t else p
+
 
 class Resize:
     """What the data path takes (DeviceBatches(resize=...), KeypointsDataset(resize=...)):

@@ -60,6 +60,23 @@ class KeypointsGauss(nn.Module):
         return yx
 
     @torch.no_grad()
+    def predict_peaks(self, x, max_peaks=4, radius=1, threshold=0.0, policy=None):
+        """Multi-peak decode (not in the reference): (peaks float32 [B,K,max_peaks,3],
+        counts int32 [B,K]) — per heatmap the up to max_peaks best local maxima with
+        score >= threshold, best first, no two within Chebyshev distance `radius` of
+        each other on the stride-8 lattice, each as (x, y, score): (x, y) like
+        soft_argmax and the labels, NOT (y, x) like predict_keypoints; sub-lattice
+        positions in input pixels, score the heatmap's value at the node; unused
+        slots (-1, -1, 0).  Same inputs as predict_keypoints (fp32 NCHW or uint8
+        NHWC); decoded from the low-res logits (ops.heat_peaks): no heatmap is
+        allocated and no upsample launch is made."""
+        from hkp import ops
+        _, _, low = net.keypoints_forward(self.resnet.net, x, self.num_keypoints, heat=False, argmax=False,
+                                          pol=policy or self.policy, upsample=False)
+        H, W = net.image_nchw_shape(x)[2:]
+        return ops.heat_peaks(low, H, W, max_peaks=max_peaks, radius=radius, threshold=threshold)
+
+    @torch.no_grad()
     def heatmaps_and_keypoints(self, x, policy=None):
         hm, yx, _ = net.keypoints_forward(self.resnet.net, x, self.num_keypoints, heat=True, argmax=True,
                                           pol=policy or self.policy)

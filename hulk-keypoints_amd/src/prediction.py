@@ -40,6 +40,13 @@ class Prediction:
         """int32 [B,K,2] (y, x) argmax per heatmap, computed on the GPU."""
         return self.model.predict_keypoints(self._batch(imgs))
 
+    def peaks(self, imgs, **kw):
+        """(float32 [B,K,P,3] (x, y, score), int32 [B,K] counts): the up to P =
+        max_peaks local maxima per heatmap with sub-pixel positions and scores,
+        computed on the GPU from the low-res logits — (x, y), not the (y, x) of
+        keypoints().  kw: max_peaks, radius, threshold (KeypointsGauss.predict_peaks)."""
+        return self.model.predict_peaks(self._batch(imgs), **kw)
+
     def softmax(self, x):
         e_x = np.exp(x - np.max(x))
         return e_x / e_x.sum()

@@ -435,6 +435,37 @@ int hkp_heat_overlay(int32_t n, int32_t k, int32_t H, int32_t W, const float* he
 int hkp_soft_argmax(int32_t n, int32_t k, int32_t H, int32_t W, float beta, const float* heat, float* out_xy,
                     hkp_stream_t stream);
 
+/* Multi-peak decode of the low-res logits (not in the reference): per plane of
+ * lowres [n,k,h,w] (fp32, what enters the upsample kernel; the full-resolution
+ * heatmap is neither read nor written) the up to max_peaks best local maxima,
+ * each as (x, y, score) — the order of soft_argmax and the labels, not the
+ * (y, x) of the argmax — in peaks [n][k][max_peaks][3] fp32, and their number
+ * in counts [n][k] int32; unused slots hold (-1, -1, 0).
+ *  order:     a NaN logit counts as -inf and -0 as +0; node a beats node b if
+ *             z[a] > z[b], or z[a] == z[b] and a has the smaller index i*w + j
+ *             (first max wins, as the argmax).
+ *  candidate: z > -inf, score = sigmoid(z) (fp32, the upsample kernel's own
+ *             function) >= threshold, and the node beats every other node of its
+ *             (2 radius + 1)^2 window clipped to the plane — the window is the
+ *             non-maximum suppression: two peaks of a plane are never within
+ *             Chebyshev distance radius.  The max_peaks best candidates are
+ *             written, best first.
+ *  position:  per axis, in fp64 from the fp32 logits, with g(z) = min(z, 0) -
+ *             log1p(exp(-|z|)) (log sigmoid: -d^2 / 2 sigma^2 for a Gaussian
+ *             target): if both neighbours lie in the plane, the three g are
+ *             finite and den = 2 g0 - g- - g+ > 1e-6, the offset is
+ *             clamp(0.5 (g+ - g-) / den, -0.5, 0.5), else 0;
+ *             x = (j + dx) (W - 1) / (w - 1) (0 when w == 1), y likewise: the
+ *             align_corners node coordinates in pixels of the H x W output, the
+ *             frame of the labels and the argmax; rounded once to fp32.
+ * One block per plane, the plane in LDS; no atomics, fixed reduction order: the
+ * same input gives the same bits.  Limits: 1 <= radius <= 8,
+ * 1 <= max_peaks <= 16, 0 <= threshold <= 1, h * w <= 32768 (128 KiB of LDS;
+ * 120 x 160 is 19200); anything else is HKP_ERR_BAD_ARG. */
+int hkp_heat_peaks(int32_t n, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W, int32_t radius,
+                   int32_t max_peaks, float threshold, const float* lowres, float* peaks, int32_t* counts,
+                   hkp_stream_t stream);
+
 /* Gaussian target (src/dataset.py:36-44): out[n,k,H,W] (fp64) =
  * (double) expf( -((x-u)^2 + (y-v)^2) / (2 sigma^2) ) computed in fp32;
  * uv [n,k,2] fp32 (u = column, v = row). */
