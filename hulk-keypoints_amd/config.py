@@ -17,7 +17,13 @@ arguments, e.g. {"max_peaks": 4, "radius": 1, "threshold": 0.1}: analysis.py als
 writes preds/peaks.npy — float32 [n_images, K, max_peaks, 3], (x, y, score) per local
 maximum of each heatmap, sub-pixel, best first, unused slots (-1, -1, 0), in each
 source image's pixels when RESIZE is set — and preds/peak_counts.npy, int32
-[n_images, K]; keypoints.npy and the overlays do not change).
+[n_images, K]; keypoints.npy and the overlays do not change), INSTANCES (None: one
+(u, v) per keypoint, clipped onto the image, as the reference; M in 1..16: the label
+files may hold [K,2], [K,3] or [K,m,3] (u, v, flag) with m <= M, a keypoint class may
+have several instances or none, points outside the image are marked absent instead
+of clipped, and the loss runs against the maximum of the instances' Gaussians,
+hkp_heat_loss_multi) and ABSENT ("zero": a keypoint that is not in the picture is
+trained against the all-zero heatmap; "ignore": its plane is left out of the loss).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -36,3 +42,5 @@ GA_PARAMS = {}
 RESIZE = None
 RESIZE_PARAMS = {}
 PEAKS = None
+INSTANCES = None
+ABSENT = "zero"

@@ -1,0 +1,275 @@
+// Multi-instance Gaussian target and loss (include/hulkkp.h has the definition).
+//
+//  * hkp_gauss_target_multi  dataset.py:36-44 with up to 16 instances per plane:
+//                    t = max over the present slots of the single Gaussian of
+//                    hkp_gauss_target (same fp32 operation order, so M = 1 gives
+//                    its bits), 0 for a plane without a present slot.
+//  * hkp_heat_loss_multi     train.py:21,25 (MSE train.py:13) against that target,
+//                    recomputed in registers: heat_loss_kernel's per-element
+//                    formulas, clamps and fp64 arithmetic.  Absent planes are
+//                    negatives (HKP_ABSENT_ZERO) or leave the mean (HKP_ABSENT_IGNORE:
+//                    dheat +0, divisor H*W*A with A counted on the device).
+//
+// A block works on one chunk of one plane (block = plane * chunks + chunk), so
+// the plane's records are read once per block: wave 0 compacts the present
+// ones into LDS, and the loop over them has a wave-uniform trip count.  Each
+// block writes one partial; the finalize sums them in index order.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace hkp {
+
+constexpr int MULTI_MAX_M = 16;
+constexpr int MULTI_CHUNKS = 64;   // blocks per plane at most (C3 shard tail: 32 planes -> 1920 blocks)
+
+// blocks per plane for `items` work items of one plane: at most MULTI_CHUNKS, and as
+// few as give every block the same number of 256-item trips
+static inline int multi_chunks(long items) {
+    const long want = (items + 255) / 256;
+    if (want <= MULTI_CHUNKS) return (int)(want < 1 ? 1 : want);
+    const long trips = (want + MULTI_CHUNKS - 1) / MULTI_CHUNKS;
+    return (int)((want + trips - 1) / trips);
+}
+
+// the present records of a plane, compacted in slot order; returns their number
+// (the same in every lane, in a scalar register).  Selected on the flag: what an
+// empty slot holds is never read into the result.
+__device__ __forceinline__ int stage_instances(const float* __restrict__ rec, int m, float* su, float* sv, int* scnt) {
+    if (threadIdx.x < 64) {   // wave 0: lane j reads record j (one load latency), a ballot compacts
+        const int j = threadIdx.x;
+        float u = 0.f, v = 0.f;
+        bool on = false;
+        if (j < m) {
+            u = rec[3 * j];
+            v = rec[3 * j + 1];
+            on = rec[3 * j + 2] > 0.f;
+        }
+        const unsigned long long mask = __ballot(on);
+        if (on) {
+            const int pos = __popcll(mask & ((1ull << j) - 1ull));
+            su[pos] = u;
+            sv[pos] = v;
+        }
+        if (j == 0) *scnt = __popcll(mask);
+    }
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(*scnt);
+}
+
+__device__ __forceinline__ double multi_block_sum_d(double v, double* red) {
+    v = wave_sum_d(v);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+    return t;
+}
+
+template <int KIND>
+__device__ __forceinline__ double loss_elem(double x, double y, double inv_n, float* g_out) {
+    double l, g;
+    if constexpr (KIND == HKP_LOSS_BCE) {
+        l = (y - 1.0) * fmax(log1p(-x), -100.0) - y * fmax(log(x), -100.0);
+        g = (x - y) / fmax((1.0 - x) * x, (double)1e-12f) * inv_n;
+    } else {
+        l = (x - y) * (x - y);
+        g = 2.0 * inv_n * (x - y);
+    }
+    *g_out = (float)g;
+    return l;
+}
+
+__global__ __launch_bounds__(256) void gauss_target_multi_kernel(int m, int H, int W, int chunks, float den,
+                                                                const float* __restrict__ pts,
+                                                                double* __restrict__ out) {
+    __shared__ float su[MULTI_MAX_M], sv[MULTI_MAX_M];
+    __shared__ int scnt;
+    const long plane = blockIdx.x / chunks;
+    const int chunk = blockIdx.x - (int)plane * chunks;
+    const int cnt = stage_instances(pts + plane * 3 * m, m, su, sv, &scnt);
+    const int HW = H * W;
+    double* o = out + plane * (long)HW;
+    for (int i = chunk * 256 + threadIdx.x; i < HW; i += chunks * 256) {
+        const int yy = i / W, xx = i - yy * W;
+        float t = 0.f;
+        for (int j = 0; j < cnt; ++j) {
+            const float dx = (float)xx - su[j], dy = (float)yy - sv[j];
+            t = fmaxf(t, expf(-(dx * dx + dy * dy) / den));
+        }
+        o[i] = (double)t;
+    }
+}
+
+// inv[0] = 1 / (H*W*A), A = planes with a present slot; 0 when there is none
+__global__ __launch_bounds__(256) void multi_active_kernel(int planes, int m, double hw, const float* __restrict__ pts,
+                                                          double* __restrict__ inv) {
+    __shared__ int red[4];
+    int c = 0;
+    for (int p = threadIdx.x; p < planes; p += 256) {
+        const float* rec = pts + (long)p * 3 * m;
+        bool any = false;
+        for (int j = 0; j < m; ++j) any = any || rec[3 * j + 2] > 0.f;
+        c += any ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int a = red[0] + red[1] + red[2] + red[3];
+        inv[0] = a > 0 ? 1.0 / (hw * (double)a) : 0.0;
+    }
+}
+
+// VEC4: W % 4 == 0 and 16-byte aligned bases: an item is 4 pixels of one row
+template <int KIND, bool VEC4>
+__global__ __launch_bounds__(256) void heat_loss_multi_kernel(int m, int H, int W, int chunks, float den,
+                                                             double inv_n_host, const double* __restrict__ inv_n_dev,
+                                                             const float* __restrict__ p,
+                                                             const float* __restrict__ pts, float* __restrict__ dheat,
+                                                             double* __restrict__ part) {
+    __shared__ float su[MULTI_MAX_M], sv[MULTI_MAX_M];
+    __shared__ int scnt;
+    __shared__ double red[4];
+    const long plane = blockIdx.x / chunks;
+    const int chunk = blockIdx.x - (int)plane * chunks;
+    const int cnt = stage_instances(pts + plane * 3 * m, m, su, sv, &scnt);
+    const int HW = H * W;
+    const float* pp = p + plane * (long)HW;
+    float* dp = dheat ? dheat + plane * (long)HW : nullptr;
+    const int first = chunk * 256 + threadIdx.x, step = chunks * 256;
+    // HKP_ABSENT_IGNORE (inv_n_dev set): a plane without a present slot leaves the loss
+    if (inv_n_dev != nullptr && cnt == 0) {
+        if (dp) {
+            if constexpr (VEC4) {
+                for (int q = first; q < (HW >> 2); q += step) ((f32x4*)dp)[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                for (int i = first; i < HW; i += step) dp[i] = 0.f;
+            }
+        }
+        if (threadIdx.x == 0) part[blockIdx.x] = 0.0;
+        return;
+    }
+    const double inv_n = inv_n_dev ? inv_n_dev[0] : inv_n_host;
+    double acc = 0.0;
+    if constexpr (VEC4) {
+        const int W4 = W >> 2;
+        for (int q = first; q < (HW >> 2); q += step) {
+            const int yy = q / W4, x0 = (q - yy * W4) * 4;
+            const f32x4 xv = ((const f32x4*)pp)[q];
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < cnt; ++j) {
+                const float u = su[j];
+                const float dy = (float)yy - sv[j];
+                const float dy2 = dy * dy;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float dx = (float)(x0 + e) - u;
+                    t[e] = fmaxf(t[e], expf(-(dx * dx + dy2) / den));
+                }
+            }
+            f32x4 gv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float g;
+                acc += loss_elem<KIND>((double)xv[e], (double)t[e], inv_n, &g);
+                gv[e] = g;
+            }
+            if (dp) ((f32x4*)dp)[q] = gv;
+        }
+    } else {
+        for (int i = first; i < HW; i += step) {
+            const int yy = i / W, xx = i - yy * W;
+            float t = 0.f;
+            for (int j = 0; j < cnt; ++j) {
+                const float dx = (float)xx - su[j], dy = (float)yy - sv[j];
+                t = fmaxf(t, expf(-(dx * dx + dy * dy) / den));
+            }
+            float g;
+            acc += loss_elem<KIND>((double)pp[i], (double)t, inv_n, &g);
+            if (dp) dp[i] = g;
+        }
+    }
+    const double s = multi_block_sum_d(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void loss_multi_finalize_kernel(int nparts, double inv_n_host,
+                                                                 const double* __restrict__ inv_n_dev,
+                                                                 const double* __restrict__ part, double* loss) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += part[i];
+    const double t = multi_block_sum_d(s, red);
+    if (threadIdx.x == 0) loss[0] = t * (inv_n_dev ? inv_n_dev[0] : inv_n_host);
+}
+
+static inline bool multi_sizes_ok(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W) {
+    // a plane is indexed with 32-bit integers, the block index too
+    return n > 0 && k > 0 && m >= 1 && m <= MULTI_MAX_M && H > 0 && W > 0 && (long)H * W <= (1L << 30) &&
+           (long)n * k * MULTI_CHUNKS <= (1L << 30);
+}
+
+}  // namespace hkp
+
+using namespace hkp;
+
+extern "C" int hkp_gauss_target_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, float sigma,
+                                      const float* pts, double* out, hkp_stream_t stream) {
+    HKP_CHECK_ARG(multi_sizes_ok(n, k, m, H, W) && sigma > 0.f,
+                  "hkp_gauss_target_multi: bad sizes (1 <= m <= 16, H*W <= 2^30)");
+    HKP_CHECK_ARG(pts && out, "hkp_gauss_target_multi: null tensor");
+    const float den = (float)(2.0 * (double)sigma * (double)sigma);
+    const int chunks = multi_chunks((long)H * W);
+    hipLaunchKernelGGL(gauss_target_multi_kernel, dim3((unsigned)(n * k * chunks)), dim3(256), 0, as_stream(stream), m,
+                       H, W, chunks, den, pts, out);
+    HKP_LAUNCH_CHECK("hkp_gauss_target_multi");
+    return HKP_OK;
+}
+
+// one double for 1 / (H*W*A), then a partial per block (at most MULTI_CHUNKS a plane)
+extern "C" int64_t hkp_heat_loss_multi_workspace(int32_t n, int32_t k, int32_t H, int32_t W) {
+    if (n <= 0 || k <= 0 || H <= 0 || W <= 0) return -1;
+    return (int64_t)(1 + (int64_t)n * k * MULTI_CHUNKS) * (int64_t)sizeof(double);
+}
+
+extern "C" int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                                   int32_t absent_mode, const float* heat, const float* pts, float sigma,
+                                   double* loss, float* dheat, void* workspace, hkp_stream_t stream) {
+    HKP_CHECK_ARG(multi_sizes_ok(n, k, m, H, W) && sigma > 0.f,
+                  "hkp_heat_loss_multi: bad sizes (1 <= m <= 16, H*W <= 2^30)");
+    HKP_CHECK_ARG(heat && pts && loss && workspace, "hkp_heat_loss_multi: null tensor");
+    HKP_CHECK_ARG(loss_kind == HKP_LOSS_BCE || loss_kind == HKP_LOSS_MSE, "hkp_heat_loss_multi: bad loss kind");
+    HKP_CHECK_ARG(absent_mode == HKP_ABSENT_ZERO || absent_mode == HKP_ABSENT_IGNORE,
+                  "hkp_heat_loss_multi: bad absent mode");
+    const int planes = n * k;
+    const long HW = (long)H * W;
+    const float den = (float)(2.0 * (double)sigma * (double)sigma);
+    const bool vec4 = W % 4 == 0 && ((uintptr_t)heat & 15) == 0 && ((uintptr_t)dheat & 15) == 0;
+    const int chunks = multi_chunks(vec4 ? HW / 4 : HW);
+    double* inv_dev = absent_mode == HKP_ABSENT_IGNORE ? (double*)workspace : nullptr;
+    double* part = (double*)workspace + 1;
+    const double inv_n = 1.0 / (double)((long)planes * HW);
+    const int nblocks = planes * chunks;
+    hipStream_t st = as_stream(stream);
+    if (inv_dev) {
+        hipLaunchKernelGGL(multi_active_kernel, dim3(1), dim3(256), 0, st, planes, m, (double)HW, pts, inv_dev);
+        HKP_LAUNCH_CHECK("hkp_heat_loss_multi(active)");
+    }
+#define HKP_LOSS_M(KD, V4)                                                                                         \
+    hipLaunchKernelGGL((heat_loss_multi_kernel<KD, V4>), dim3((unsigned)nblocks), dim3(256), 0, st, m, H, W, chunks, \
+                       den, inv_n, inv_dev, heat, pts, dheat, part)
+    if (loss_kind == HKP_LOSS_BCE) {
+        if (vec4) HKP_LOSS_M(HKP_LOSS_BCE, true); else HKP_LOSS_M(HKP_LOSS_BCE, false);
+    } else {
+        if (vec4) HKP_LOSS_M(HKP_LOSS_MSE, true); else HKP_LOSS_M(HKP_LOSS_MSE, false);
+    }
+#undef HKP_LOSS_M
+    HKP_LAUNCH_CHECK("hkp_heat_loss_multi");
+    hipLaunchKernelGGL(loss_multi_finalize_kernel, dim3(1), dim3(256), 0, st, nblocks, inv_n, inv_dev, part, loss);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_multi(finalize)");
+    return HKP_OK;
+}

@@ -15,6 +15,9 @@ HKP_LAYOUT_NHWC = 0
 HKP_LAYOUT_NCHW = 1
 HKP_LOSS_BCE = 0
 HKP_LOSS_MSE = 1
+HKP_ABSENT_ZERO = 0
+HKP_ABSENT_IGNORE = 1
+MAX_INSTANCES = 16                 # slots per plane of the multi-instance labels (hkp_heat_peaks' max_peaks limit)
 
 
 class HkpError(RuntimeError):
@@ -185,6 +188,10 @@ SIGNATURES = {
     "hkp_maxpool_bwd": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "hkp_heat_loss_workspace": (_I64, []),
     "hkp_heat_loss": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _P, _P, _P, _P]),
+    # multi-instance labels pts [n,k,m,3] (u, v, flag)
+    "hkp_gauss_target_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
+    "hkp_heat_loss_multi_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "hkp_heat_loss_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P, _P]),
     "hkp_head_bwd_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "hkp_head_bwd": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "hkp_head_fc_bwd_workspace": (_I64, [_I32, _I32, _I32, _I32]),

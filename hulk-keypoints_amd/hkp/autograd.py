@@ -53,9 +53,30 @@ class _HeatLossFn(torch.autograd.Function):
         return dheat * g.to(dheat.dtype), None, None, None, None
 
 
-def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce"):
+class _HeatLossMultiFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, heat, pts, sigma, kind, absent):
+        loss, dheat = ops.heat_loss_multi(heat.contiguous(), pts, sigma, kind, absent,
+                                          want_grad=torch.is_grad_enabled() or heat.requires_grad)
+        ctx.save_for_backward(dheat)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dheat,) = ctx.saved_tensors
+        return dheat * g.to(dheat.dtype), None, None, None, None
+
+
+def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero"):
     """mean BCE (default) or MSE between fp32 heatmaps and the fp64 Gaussian target
-    (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor."""
+    (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor.
+    ``pts`` [N,K,M,3] (u, v, flag) in place of both: the multi-instance target
+    (ops.heat_loss_multi), planes without a present instance handled per ``absent``
+    ("zero": negatives; "ignore": left out of the mean)."""
+    if pts is not None:
+        if target is not None or uv is not None:
+            raise ops.HkpError("heatmap_loss: pass pts alone, not with target or uv")
+        return _HeatLossMultiFn.apply(heat, pts, sigma, kind, absent)
     return _HeatLossFn.apply(heat, target, uv, sigma, kind)
 
 

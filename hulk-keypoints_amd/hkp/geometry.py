@@ -170,6 +170,36 @@ class WarpPlan:
         out[..., 1] = np.clip(out[..., 1], 0, h - 1)
         return torch.from_numpy(out) if is_t else out
 
+    def apply_points(self, pts):
+        """Instance labels through the batch's transforms: pts [n, K, M, 3] on the host
+        (u, v, flag; numpy or a CPU tensor, the same kind comes back, float32).  (u, v)
+        of the present slots (flag > 0) go through the forward matrix, rows of
+        `flip_pairs` are exchanged along K (whole [M, 3] rows) where the image was
+        flipped, and a present point that leaves [0, w-1] x [0, h-1] — the range
+        apply_uv clips to — gets flag 0; it is not clipped.  Empty slots pass through
+        as they are."""
+        is_t, a = host_points(pts, self.n, "apply_points")
+        out = np.array(a, dtype=np.float32, copy=True)
+        h, w = self.hw
+        for b in range(self.n):
+            on = out[b, :, :, 2] > 0
+            q = transform_uv(self.matrices[b], np.where(on[..., None], out[b, :, :, :2], 0.0))
+            inside = (q[..., 0] >= 0) & (q[..., 0] <= w - 1) & (q[..., 1] >= 0) & (q[..., 1] <= h - 1)
+            out[b, :, :, :2] = np.where(on[..., None], q, out[b, :, :, :2])
+            out[b, :, :, 2] = np.where(on & ~inside, 0.0, out[b, :, :, 2])
+            if self.flipped[b]:
+                out[b] = swap_pairs(out[b], self.flip_pairs)
+        return torch.from_numpy(out) if is_t else out
+
+
+def host_points(pts, n, who):
+    """(is a tensor, numpy view) of instance labels [n, K, M, 3] on the host."""
+    is_t = isinstance(pts, torch.Tensor)
+    a = pts.detach().cpu().numpy() if is_t else np.asarray(pts)
+    if a.ndim != 4 or a.shape[0] != n or a.shape[3] != 3:
+        raise HkpError("%s: expected instance labels [%d, K, M, 3], got %s" % (who, n, a.shape))
+    return is_t, a
+
 
 # ---------------------------------------------------------------- sampling ----
 class GeometricAugmentation:
@@ -250,19 +280,26 @@ class GeometricAugmentation:
         return affine_matrix(h, w, p["rotate"], p["scale"], (p["translate"][0] * w, p["translate"][1] * h),
                              p["shear"], p["hflip"], p["vflip"])
 
-    def sample(self, index, epoch=0, uv=None, hw=None):
+    def sample(self, index, epoch=0, uv=None, hw=None, pts=None):
         """The parameters of sample `index` in `epoch`: a dict with "rotate", "scale",
         "translate" (fractions), "shear", "hflip", "vflip" and "try" (which draw was
         taken; -1: the identity, after `tries` draws left a keypoint outside).  uv
-        [K, 2] and hw = (h, w) switch the keep_inside search on."""
+        [K, 2] and hw = (h, w) switch the keep_inside search on; so do instance labels
+        pts [K, M, 3] (u, v, flag) in place of uv, of which only the present slots
+        (flag > 0) are tested.  The draws are the same either way."""
+        if uv is not None and pts is not None:
+            raise HkpError("GeometricAugmentation.sample: pass uv or pts, not both")
         rng = np.random.default_rng([self.seed, int(epoch), int(index), 1])
-        if uv is None or not self.keep_inside:
+        if (uv is None and pts is None) or not self.keep_inside:
             p = self._draw(rng)
             p["try"] = 0
             return p
         if hw is None:
             raise HkpError("GeometricAugmentation.sample: keep_inside with labels needs hw=(h, w)")
         h, w = hw
+        if pts is not None:
+            rec = np.asarray(pts).reshape(-1, 3)
+            uv = rec[rec[:, 2] > 0, :2]
         pts = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
         for t in range(self.tries):
             p = self._draw(rng)
@@ -273,12 +310,24 @@ class GeometricAugmentation:
         return {"rotate": 0.0, "scale": 1.0, "translate": (0.0, 0.0), "shear": 0.0, "hflip": False, "vflip": False,
                 "try": -1}
 
-    def plan(self, indices, epoch=0, uvs=None, hw=None):
+    def plan(self, indices, epoch=0, uvs=None, hw=None, pts=None):
         """The WarpPlan of one batch: sample `indices[b]` of `epoch` for image b of
-        size hw = (h, w); uvs [B, K, 2] (host) feeds keep_inside."""
+        size hw = (h, w); uvs [B, K, 2] (host), or instance labels pts [B, K, M, 3] in
+        their place (also accepted as uvs), feeds keep_inside."""
         if hw is None:
             raise HkpError("GeometricAugmentation.plan: hw=(h, w) is required")
         indices = [int(i) for i in indices]
+        if uvs is not None and pts is None and np.ndim(uvs) == 4:
+            uvs, pts = None, uvs
+        if pts is not None:
+            if uvs is not None:
+                raise HkpError("GeometricAugmentation.plan: pass uvs or pts, not both")
+            _, pa = host_points(pts, len(indices), "GeometricAugmentation.plan")
+            ps = [self.sample(i, epoch, hw=hw, pts=pa[b]) for b, i in enumerate(indices)]
+            plan = WarpPlan([self.matrix(p, hw) for p in ps], hw, flipped=[p["hflip"] != p["vflip"] for p in ps],
+                            flip_pairs=self.flip_pairs, fill=self.fill, interp=self.interp, border=self.border)
+            plan.params = ps
+            return plan
         if uvs is not None:
             uvs = uvs.detach().cpu().numpy() if isinstance(uvs, torch.Tensor) else np.asarray(uvs)
             if uvs.ndim != 3 or uvs.shape[0] != len(indices) or uvs.shape[2] != 2:
@@ -290,7 +339,14 @@ class GeometricAugmentation:
         plan.params = ps
         return plan
 
-    def __call__(self, img, uv=None, index=None, epoch=None):
+    def __call__(self, img, uv=None, index=None, epoch=None, pts=None):
+        """pts ([B,K,M,3] / [K,M,3] instance labels: u, v, flag) in place of uv: (img, pts)
+        comes back, the labels through WarpPlan.apply_points."""
+        if uv is not None and pts is not None:
+            raise HkpError("GeometricAugmentation: pass uv or pts, not both")
+        is_pts = pts is not None
+        if is_pts:
+            uv = pts
         if torch.utils.data.get_worker_info() is not None:
             raise HkpError("GeometricAugmentation runs on the GPU and DataLoader workers never touch the device: "
                            "keep num_workers=0 for this transform, or use DeviceBatches(geometric=...) "
@@ -316,7 +372,7 @@ class GeometricAugmentation:
         uv_a = None
         if uv is not None:
             uv_a = (uv.detach().cpu().numpy() if uv_t else np.asarray(uv)).astype(np.float32)
-            squeeze = single and uv_a.ndim == 2
+            squeeze = single and uv_a.ndim == (3 if is_pts else 2)
             if squeeze:
                 uv_a = uv_a[None]
         if index is None:
@@ -324,7 +380,8 @@ class GeometricAugmentation:
             self._calls += n
         else:
             indices = [int(index)] if np.ndim(index) == 0 else [int(i) for i in index]
-        plan = self.plan(indices, self.epoch if epoch is None else epoch, uvs=uv_a, hw=(h, w))
+        plan = self.plan(indices, self.epoch if epoch is None else epoch, uvs=None if is_pts else uv_a,
+                         pts=uv_a if is_pts else None, hw=(h, w))
         out = ops.warp_affine_u8(x, plan)
         if single:
             out = out[0]
@@ -333,7 +390,7 @@ class GeometricAugmentation:
         out = out.cpu().numpy() if is_np else out
         if uv is None:
             return out
-        new = plan.apply_uv(uv_a)
+        new = plan.apply_points(uv_a) if is_pts else plan.apply_uv(uv_a)
         if squeeze:
             new = new[0]
         return out, (torch.from_numpy(new).to(uv.device) if uv_t else new)

@@ -987,6 +987,26 @@ def gauss_target(uv, H, W, sigma):
     return out
 
 
+def _need_pts(pts, name):
+    """Instance labels float32 [N,K,M,3] (u, v, flag), 1 <= M <= 16, on the GPU."""
+    from ._lib import MAX_INSTANCES
+    _need(pts, torch.float32, name, 4)
+    if pts.shape[3] != 3 or not 1 <= pts.shape[2] <= MAX_INSTANCES or pts.shape[0] < 1 or pts.shape[1] < 1:
+        raise HkpError("%s: expected [N,K,M,3] with 1 <= M <= %d, got %s" % (name, MAX_INSTANCES, tuple(pts.shape)))
+
+
+def gauss_target_multi(pts, H, W, sigma):
+    """pts float32 [N,K,M,3] (u=x, v=y, flag; flag > 0: present) → float64 [N,K,H,W]:
+    the maximum of the present instances' Gaussians, 0 for a plane with none."""
+    _need_pts(pts, "gauss_target_multi.pts")
+    n, k, m, _ = pts.shape
+    if int(H) < 1 or int(W) < 1 or not float(sigma) > 0:
+        raise HkpError("gauss_target_multi: bad size %sx%s or sigma %s" % (H, W, sigma))
+    out = torch.empty((n, k, int(H), int(W)), device=pts.device, dtype=torch.float64)
+    call("hkp_gauss_target_multi", n, k, m, int(H), int(W), float(sigma), _ptr(pts), _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------ backward
 
 
@@ -1400,6 +1420,37 @@ def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True)
     dheat = torch.empty_like(heat) if want_grad else None
     call("hkp_heat_loss", n, k, H, W, HKP_LOSS_BCE if kind == "bce" else HKP_LOSS_MSE, _ptr(heat), _ptr(target),
          _ptr(uv), float(sigma), _ptr(loss), _ptr(dheat), _ptr(ws), _stream())
+    return loss, dheat
+
+
+ABSENT_MODES = ("zero", "ignore")
+
+
+def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True):
+    """heat_loss against the multi-instance target of pts float32 [N,K,M,3] (u, v,
+    flag), recomputed in registers → (loss 0-dim f64 tensor, dheat f32 or None).
+    absent="zero": a plane without a present slot is trained against zeros;
+    "ignore": it contributes nothing (dheat +0) and the mean runs over the other
+    planes' elements (counted on the device; none: loss 0)."""
+    from ._lib import HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, lib
+    _need(heat, torch.float32, "heat_loss_multi.heat", 4)
+    _need_pts(pts, "heat_loss_multi.pts")
+    n, k, H, W = heat.shape
+    if tuple(pts.shape[:2]) != (n, k) or pts.device != heat.device:
+        raise HkpError("heat_loss_multi: pts %s on %s does not go with heat %s on %s"
+                       % (tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
+    if kind not in ("bce", "mse"):
+        raise HkpError("heat_loss_multi: unknown kind %r (known: bce, mse)" % (kind,))
+    if absent not in ABSENT_MODES:
+        raise HkpError("heat_loss_multi: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
+    if heat.numel() == 0 or not float(sigma) > 0:
+        raise HkpError("heat_loss_multi: empty heat or sigma %s" % (sigma,))
+    ws = torch.empty(lib().hkp_heat_loss_multi_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
+    loss = torch.empty((), device=heat.device, dtype=torch.float64)
+    dheat = torch.empty_like(heat) if want_grad else None
+    call("hkp_heat_loss_multi", n, k, pts.shape[2], H, W, HKP_LOSS_BCE if kind == "bce" else HKP_LOSS_MSE,
+         HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE, _ptr(heat), _ptr(pts), float(sigma), _ptr(loss),
+         _ptr(dheat), _ptr(ws), _stream())
     return loss, dheat
 
 

@@ -262,6 +262,25 @@ class ResamplePlan:
         out = out.astype(np.float32)
         return torch.from_numpy(out) if is_t else out
 
+    def apply_points(self, pts):
+        """Instance labels pts [n, K, M, 3] (u, v, flag) in source pixels (numpy or a CPU
+        tensor; the same kind comes back, float32) -> output pixels, in `stretch` and
+        `fit` modes alike: (u, v) of the present slots (flag > 0) through apply_uv's
+        map; a present point that leaves [0, w-1] x [0, h-1] gets flag 0 and is not
+        clipped; empty slots pass through as they are."""
+        from .geometry import host_points
+        is_t, a = host_points(pts, self.n, "apply_points")
+        out = np.array(a, dtype=np.float32, copy=True)
+        gain, org = self._maps()
+        on = out[..., 2] > 0
+        src = np.where(on[..., None], out[..., :2], 0.0).astype(np.float64)
+        q = ((src + 0.5) * gain[:, None] - 0.5 + org[:, None]).astype(np.float32)
+        h, w = self.hw
+        inside = (q[..., 0] >= 0) & (q[..., 0] <= w - 1) & (q[..., 1] >= 0) & (q[..., 1] <= h - 1)
+        out[..., :2] = np.where(on[..., None], q, out[..., :2])
+        out[..., 2] = np.where(on & ~inside, 0.0, out[..., 2])
+        return torch.from_numpy(out) if is_t else out
+
     def invert_uv(self, uv):
         """Predictions uv [n, K, 2] in output pixels -> the source image's pixels (not clipped)."""
         is_t, a = _host_uv(uv, self.n, "invert_uv")

@@ -130,8 +130,14 @@ class Trainer:
     """One optimizer step per call, reference semantics (train.py:33-36)."""
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-4, loss="bce", sigma=8.0, distributed=False,
-                 bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False):
-        """sync_bn: BN statistics and their backward sums over every rank of
+                 bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False, absent="zero"):
+        """absent: what a plane of multi-instance labels (pts [B,K,M,3]: u, v, flag) without
+        a present instance does: "zero" trains it against the all-zero target, "ignore"
+        leaves it out of the loss (its gradient is zero, the mean runs over the other
+        planes).  Under data parallelism "ignore" divides by each rank's own count of
+        active planes, so the all-reduced gradient is the mean of the per-rank means
+        (DDP semantics), not the mean over the global batch's active planes.
+        sync_bn: BN statistics and their backward sums over every rank of
         `group` (default: the world; the step then equals one step over the
         global batch), instead of per-rank BN (DDP semantics, the default).
         force_buckets: the DP gradient path (bucket copies, stream joins) at world
@@ -155,6 +161,9 @@ class Trainer:
         self.params = list(model.parameters())
         self.loss_kind = loss
         self.sigma = sigma
+        if absent not in ops.ABSENT_MODES:
+            raise ValueError("absent must be one of %s, got %r" % (", ".join(ops.ABSENT_MODES), absent))
+        self.absent = absent
         if optimizer not in ("fused", "torch"):
             raise ValueError("optimizer must be 'fused' or 'torch'")
         opt_cls = FusedAdam if optimizer == "fused" else torch.optim.Adam
@@ -165,8 +174,10 @@ class Trainer:
         self.bucketer = GradBucketer(self.params, bucket_mb << 20, group=group) if (use_dp or force_buckets) \
             else None
 
-    def forward_backward(self, x, uv=None, target=None, global_batch=None):
-        """global_batch (SyncBN): the job's batch size — the same on every rank, x
+    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None):
+        """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
+        flag: the multi-instance target, absent planes per Trainer(absent=...)).
+        global_batch (SyncBN): the job's batch size — the same on every rank, x
         being this rank's hkp.parallel.shard_range share of it; lets the empty-shard
         guard run without a host collective (parallel.ShardCheck)."""
         if self.sync_bn:
@@ -174,7 +185,12 @@ class Trainer:
         m = self.model
         trace = net.Trace(self.policy)
         hm, _, _ = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace)
-        loss, dheat = ops.heat_loss(hm, target, uv, self.sigma, self.loss_kind, want_grad=True)
+        if pts is not None:
+            if uv is not None or target is not None:
+                raise ops.HkpError("Trainer: pass pts alone, not with uv or target")
+            loss, dheat = ops.heat_loss_multi(hm, pts, self.sigma, self.loss_kind, self.absent, want_grad=True)
+        else:
+            loss, dheat = ops.heat_loss(hm, target, uv, self.sigma, self.loss_kind, want_grad=True)
         grads = net.Grads(on_ready=self.bucketer.ready if self.bucketer else None)
         net.keypoints_backward(m.resnet.net, trace, dheat, grads)
         if self.bucketer is not None:
@@ -184,7 +200,7 @@ class Trainer:
                 p.grad = grads[p]
         return loss
 
-    def step(self, x, uv=None, target=None, global_batch=None):
-        loss = self.forward_backward(x, uv, target, global_batch)
+    def step(self, x, uv=None, target=None, global_batch=None, pts=None):
+        loss = self.forward_backward(x, uv, target, global_batch, pts=pts)
         self.opt.step()
         return loss

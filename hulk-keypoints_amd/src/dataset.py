@@ -102,8 +102,17 @@ def vis_gauss(gaussians):
 
 class KeypointsDataset(Dataset):
     def __init__(self, img_folder, labels_folder, num_keypoints, img_height, img_width, transform, gauss_sigma=8,
-                 return_uv=False, device="cuda", geometric=None, resize=None):
-        """geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, the decoded
+                 return_uv=False, device="cuda", geometric=None, resize=None, instances=None):
+        """instances: None (the reference's labels: one (u, v) per keypoint, clipped onto the
+        image), or M (1..16): multi-instance labels pts [K,M,3] (u, v, flag; flag > 0: the
+        slot holds an instance).  A label file may then be [K,2] (every keypoint present
+        once), [K,3] or [K,m,3] with m <= M; it is padded with empty slots.  Labels are
+        not clipped: a present point outside the image is marked absent (flag 0) — with
+        `resize`, after the resize has mapped it.  Items are (img, pts) with
+        return_uv=True, else (img, gaussians) from hkp_gauss_target_multi; raw() returns
+        pts.
+
+        geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, the decoded
         uint8 image and the host label go through it (on the GPU: keep num_workers=0)
         before `transform`, under the sample's own index and the epoch of set_epoch();
         the returned uv / Gaussians come from the transformed label.
@@ -123,10 +132,19 @@ class KeypointsDataset(Dataset):
         self.gauss_sigma = gauss_sigma
         self.transform = transform
         self.return_uv = return_uv
+        if instances is not None and not 1 <= int(instances) <= 16:
+            raise ValueError("instances must be None or 1..16, got %r" % (instances,))
+        self.instances = None if instances is None else int(instances)
         self.imgs = []
         self.labels = []
         self.labels_np = []           # host copies (DataLoader workers never touch the device)
         for i in range(len(os.listdir(labels_folder))):
+            if self.instances is not None:
+                label = self._load_instances(os.path.join(labels_folder, "%05d.npy" % i))
+                self.imgs.append(os.path.join(img_folder, "%05d.jpg" % i))
+                self.labels.append(torch.from_numpy(label).to(device))
+                self.labels_np.append(label)
+                continue
             label = np.load(os.path.join(labels_folder, "%05d.npy" % i)).reshape(num_keypoints, 2)
             if resize is None:
                 label[:, 0] = np.clip(label[:, 0], 0, self.img_width - 1)      # dataset.py:65
@@ -134,6 +152,33 @@ class KeypointsDataset(Dataset):
             self.imgs.append(os.path.join(img_folder, "%05d.jpg" % i))
             self.labels.append(torch.from_numpy(label).to(device))
             self.labels_np.append(label.astype(np.float32))
+
+    def _load_instances(self, path):
+        """One label file as float32 [K, M, 3], padded with empty slots (0, 0, 0)."""
+        K, M = self.num_keypoints, self.instances
+        a = np.load(path)
+        if a.shape == (K, 2):
+            a = np.concatenate([a, np.ones((K, 1), dtype=a.dtype)], 1)[:, None, :]
+        elif a.shape == (K, 3):
+            a = a[:, None, :]
+        if a.ndim != 3 or a.shape[0] != K or a.shape[2] != 3 or not 1 <= a.shape[1] <= M:
+            raise ValueError("%s: expected labels [%d,2], [%d,3] or [%d,m,3] with m <= %d, got %s"
+                             % (path, K, K, K, M, a.shape))
+        out = np.zeros((K, M, 3), dtype=np.float32)
+        out[:, :a.shape[1]] = a
+        if self.resize is None:
+            out = self._mark_outside(out)
+        return out
+
+    def _mark_outside(self, pts):
+        """Present points outside [0, w-1] x [0, h-1] lose their flag (not clipped)."""
+        on = pts[..., 2] > 0
+        with np.errstate(invalid="ignore"):
+            inside = ((pts[..., 0] >= 0) & (pts[..., 0] <= self.img_width - 1) & (pts[..., 1] >= 0)
+                      & (pts[..., 1] <= self.img_height - 1))
+        pts = pts.copy()
+        pts[..., 2] = np.where(on & ~inside, 0.0, pts[..., 2])
+        return pts
 
     def set_epoch(self, epoch):
         """The epoch the geometric augmentation draws under (train.py's fit() calls it)."""
@@ -149,9 +194,12 @@ class KeypointsDataset(Dataset):
             plan = self.resize.plan([img.shape[:2]], (self.img_height, self.img_width))
             flat = torch.from_numpy(np.ascontiguousarray(img).reshape(-1)).to(self.device)
             img = ops.resample_ragged_u8(flat, plan)[0].cpu().numpy()
-            uv = plan.apply_uv(uv[None])[0]
+            uv = (plan.apply_points(uv[None]) if self.instances is not None else plan.apply_uv(uv[None]))[0]
         if self.geometric is not None:
-            img, uv = self.geometric(img, uv, index=index, epoch=self.epoch)
+            if self.instances is not None:
+                img, uv = self.geometric(img, pts=uv, index=index, epoch=self.epoch)
+            else:
+                img, uv = self.geometric(img, uv, index=index, epoch=self.epoch)
         return img, torch.from_numpy(uv).to(self.device)
 
     def __getitem__(self, index):
@@ -159,13 +207,17 @@ class KeypointsDataset(Dataset):
         img = self.transform(img)
         if self.return_uv:
             return img, labels.float()
+        if self.instances is not None:
+            pts = labels.float().unsqueeze(0).contiguous()
+            return img, ops.gauss_target_multi(pts, self.img_height, self.img_width, self.gauss_sigma)[0]
         U = labels[:, 0]
         V = labels[:, 1]
         gaussians = gauss_2d_batch(self.img_width, self.img_height, self.gauss_sigma, U, V)
         return img, gaussians
 
     def raw(self, index):
-        """(uint8 [H,W,3] BGR image as cv2.imread gives, fp32 [K,2] (u, v) on the device)."""
+        """(uint8 [H,W,3] BGR image as cv2.imread gives, fp32 [K,2] (u, v) on the device;
+        with instances=M: fp32 [K,M,3] (u, v, flag))."""
         img, labels = self._decode(index)
         return img, labels.float()
 
@@ -303,6 +355,11 @@ class DeviceBatches:
     `augment` leaves the labels untouched (every one of its operators keeps the
     geometry).
 
+    A dataset built with instances=M carries labels pts [K,M,3] (u, v, flag): the
+    batches are then (img, pts fp32 [B,K,M,3]) for Trainer.step(img, pts=pts), and
+    `geometric` / `resize` move them with plan.apply_points (a point that leaves the
+    image becomes absent) instead of apply_uv.
+
     geometric: a hkp.geometry.GeometricAugmentation, or None.  When set, each batch is
     warped on the copy stream after its copy / JPEG reconstruct and before `augment`,
     image b under the transform of (geometric.seed, this epoch, its dataset index,
@@ -409,12 +466,12 @@ class DeviceBatches:
                         rsizes = [(img.shape[1], img.shape[2])] * img.shape[0]
                     rplan = self.resize.plan(rsizes, (self.ds.img_height, self.ds.img_width))
                     img = ops.resample_ragged_u8(img.reshape(-1), rplan)
-                    uv = rplan.apply_uv(uv).pin_memory()
+                    uv = (rplan.apply_points(uv) if uv.dim() == 4 else rplan.apply_uv(uv)).pin_memory()
                     buf = (buf, rplan, uv)     # the plan's pinned records and tables live as long as the batch's
                 if self.geometric is not None:
                     gplan = self.geometric.plan(idx, epoch, uvs=uv, hw=(img.shape[1], img.shape[2]))
                     img = ops.warp_affine_u8(img, gplan)
-                    uv = gplan.apply_uv(uv).pin_memory()
+                    uv = (gplan.apply_points(uv) if uv.dim() == 4 else gplan.apply_uv(uv)).pin_memory()
                     buf = (buf, gplan, uv)     # the plan's pinned records and the labels live as long as the batch's
                 if self.augment is not None:
                     plan = self.augment.plan(idx, epoch)

@@ -21,8 +21,9 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import (BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GA_PARAMS, GA_SEED, GAUSS_SIGMA, GEOMETRIC_AUGMENTATION,
-                    IMG_HEIGHT, IMG_WIDTH, LOSS, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
+from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
+                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS,
+                    batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp.train import GradBucketer, broadcast_state
 from src.dataset import KeypointsDataset, domain_randomization, transform
@@ -44,6 +45,10 @@ def forward(sample_batched, model):
     pred_gauss = model.forward(img)
     if gt.dim() == 3:   # (u, v) labels → the loss kernel recomputes the Gaussian target in registers
         return hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS)
+    if gt.dim() == 4 and gt.shape != pred_gauss.shape and gt.shape[-1] == 3 and gt.is_floating_point():
+        # instance labels [B,K,M,3] (u, v, flag): the multi-instance target, absent planes per ABSENT
+        return hkp_autograd.heatmap_loss(pred_gauss, pts=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
+                                         absent=ABSENT)
     return hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS)
 
 
@@ -123,10 +128,10 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
         resize = Resize(filter=RESIZE, **RESIZE_PARAMS)
     train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir, "data/%s/train/keypoints" % dataset_dir,
                                      NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA,
-                                     return_uv=True, geometric=geometric, resize=resize)
+                                     return_uv=True, geometric=geometric, resize=resize, instances=INSTANCES)
     test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
-                                    return_uv=True, resize=resize)
+                                    return_uv=True, resize=resize, instances=INSTANCES)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset) if world > 1 else None
     train_data = DataLoader(train_dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
                             num_workers=workers)

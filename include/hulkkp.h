@@ -682,6 +682,38 @@ int hkp_heat_loss(int32_t n, int32_t k, int32_t H, int32_t W, int32_t loss_kind,
                   const double* target, const float* uv, float sigma, double* loss, float* dheat, void* workspace,
                   hkp_stream_t stream);
 
+/* Multi-instance labels: pts [n,k,m,3] fp32, last axis (u, v, flag), 1 <= m <= 16
+ * (the max_peaks limit of hkp_heat_peaks).  flag > 0: the slot holds an instance at
+ * (u, v) (u = column, v = row, integers are pixel centres; finite, may lie outside
+ * the image).  Anything else: the slot is empty, and its u, v (NaN included) are
+ * never read into the result; slots need not be packed.  A plane without a present
+ * slot is an absent keypoint.
+ *
+ * Target (src/dataset.py:36-44 per instance): out[n,k,H,W] (fp64) =
+ * max over the present slots of (double) expf( -((x-u)^2 + (y-v)^2) / (2 sigma^2) ),
+ * each term in hkp_gauss_target's fp32 operation order (m = 1: its bits), 0 for an
+ * absent plane.  The maximum, not the sum: every instance keeps a peak of 1, and
+ * near a peak log t is the parabola hkp_heat_peaks refines on. */
+int hkp_gauss_target_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, float sigma, const float* pts,
+                           double* out, hkp_stream_t stream);
+
+/* hkp_heat_loss (train.py:21,25; MSE train.py:13) against that target, recomputed
+ * in registers (dataset.py:36-44): the same per-element formulas, clamps and fp64
+ * arithmetic; dheat fp32 (nullable).  absent_mode: HKP_ABSENT_ZERO trains an absent
+ * plane against the all-zero target (divisor n*k*H*W, as hkp_heat_loss);
+ * HKP_ABSENT_IGNORE leaves it out: its dheat is +0.0f and the divisor is H*W*A, A =
+ * the planes with a present slot, counted on the device (no host synchronisation);
+ * A = 0 gives loss 0 and dheat 0.  One partial per block summed in index order, no
+ * atomics: the same input gives the same bits.  Limits: 1 <= m <= 16,
+ * H*W <= 2^30; anything else is HKP_ERR_BAD_ARG.
+ * workspace: hkp_heat_loss_multi_workspace(n, k, H, W) bytes. */
+#define HKP_ABSENT_ZERO 0
+#define HKP_ABSENT_IGNORE 1
+int64_t hkp_heat_loss_multi_workspace(int32_t n, int32_t k, int32_t H, int32_t W);
+int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind, int32_t absent_mode,
+                        const float* heat, const float* pts, float sigma, double* loss, float* dheat, void* workspace,
+                        hkp_stream_t stream);
+
 /* dlow = upsample-adjoint( dheat * (1-heat) * heat ) (sigmoid backward fused;
  * heat NULL = dheat is already the pre-sigmoid gradient): a row gather into
  * `workspace` (hkp_head_bwd_workspace bytes: [n*k][H][w] floats), then a column
