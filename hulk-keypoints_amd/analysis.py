@@ -26,6 +26,18 @@ the same forward's low-res logits also go through the multi-peak decode
 RESIZE in each source image's pixels, unrounded) and preds/peak_counts.npy (int32
 [n_images, K]), file order, all-gathered like the keypoints.  keypoints.npy and the
 overlays are what they are without it.
+
+With config.EVAL set and a label directory given (main's label_dir, or a third
+command-line argument) the decoded peaks (EVAL's max_peaks / radius / threshold) are
+also matched on the GPU to each image's labels and accumulated
+(hkp.metrics.KeypointMetrics): labels are paired with the images by name as
+KeypointsDataset pairs them (<image stem>.npy) and read as KeypointsDataset(instances=...)
+reads them ([K,2], [K,3] or [K,m,3] (u, v, flag)).  Each rank accumulates its own
+shard, the integer accumulators are summed once over the ranks (all_reduce), and rank 0
+writes preds/metrics.json: KeypointMetrics.compute()'s dict (nan as null).  With
+RESIZE set the peaks are mapped to each source image's pixels before the matching and
+the labels are in source pixels, so EVAL's thresholds are distances in SOURCE pixels.
+Everything else written is what it is without EVAL.
 """
 import os
 import sys
@@ -34,14 +46,22 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from config import BACKBONE, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS, PEAKS, RESIZE, RESIZE_PARAMS
+from config import BACKBONE, EVAL, IMG_HEIGHT, IMG_WIDTH, NUM_KEYPOINTS, PEAKS, RESIZE, RESIZE_PARAMS
 from hkp import net, ops, parallel
 from src.dataset import imread_bgr, transform
 from src.model import KeypointsGauss
 from src.prediction import Prediction
 
 
-def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoints"):
+def _json_safe(v):
+    if isinstance(v, dict):
+        return {k: _json_safe(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_json_safe(x) for x in v]
+    return None if isinstance(v, float) and v != v else v
+
+
+def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoints", label_dir=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     own_group = world > 1 and not dist.is_initialized()
     if world > 1:
@@ -63,6 +83,10 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
     lo, hi = parallel.shard_range(len(files), parallel.rank(), parallel.world())
     kps, pks, cts = [], [], []
     npk = int(PEAKS.get("max_peaks", 4)) if PEAKS is not None else 0
+    metrics = eval_kw = None
+    if EVAL is not None and label_dir:
+        from hkp.metrics import from_config, load_labels
+        metrics, eval_kw = from_config(EVAL, NUM_KEYPOINTS, device="cuda")
     for i in range(lo, hi):
         img = imread_bgr(os.path.join(image_dir, files[i]))
         print(img.shape)
@@ -74,16 +98,23 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
             img = ops.resample_ragged_u8(flat, plan)[0].cpu().numpy()
         img_t = transform(img).cuda()
         with torch.no_grad():
-            if PEAKS is None:
+            if PEAKS is None and metrics is None:
                 heatmap, kp = keypoints.heatmaps_and_keypoints(img_t.view(-1, *img_t.shape))
             else:                                    # the same forward; its low-res logits feed the peak decode
                 heatmap, kp, low = net.keypoints_forward(keypoints.resnet.net, img_t.view(-1, *img_t.shape),
                                                          NUM_KEYPOINTS, heat=True, argmax=True, pol=keypoints.policy)
+            if PEAKS is not None:
                 pk, ct = ops.heat_peaks(low, IMG_HEIGHT, IMG_WIDTH, **PEAKS)
                 if plan is not None:                 # (x, y) of the used slots -> the source image's pixels
                     pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
                 pks.append(pk[0])
                 cts.append(ct[0])
+            if metrics is not None:                  # EVAL's own decode, matched to this image's labels
+                pk, ct = ops.heat_peaks(low, IMG_HEIGHT, IMG_WIDTH, **eval_kw)
+                if plan is not None:
+                    pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
+                lab = load_labels(os.path.join(label_dir, os.path.splitext(files[i])[0] + ".npy"), NUM_KEYPOINTS)
+                metrics.update(pk, ct, torch.from_numpy(lab[None]).to(pk.device))
         prediction.plot(img, heatmap.cpu().numpy(), image_id=i, keypoints=kp.cpu().numpy(), out_dir=out_dir)
         if plan is not None:                         # (y, x) on the resampled frame -> the source image's pixels
             uv = plan.invert_uv(kp[:1].cpu().numpy()[..., ::-1].astype(np.float32))
@@ -96,9 +127,15 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
                                                             device="cuda")
         local_ct = torch.stack(cts) if cts else torch.zeros((0, NUM_KEYPOINTS), dtype=torch.int32, device="cuda")
         all_pk, all_ct = (t.cpu().numpy() for t in parallel.gather_peaks(local_pk, local_ct))
+    if metrics is not None:
+        metrics.all_reduce()
     if parallel.rank() == 0:
         os.makedirs(out_dir, exist_ok=True)
         np.save(os.path.join(out_dir, "keypoints.npy"), all_kp)
+        if metrics is not None:
+            import json
+            with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+                json.dump(_json_safe(metrics.compute()), f, indent=1)
         if PEAKS is not None:
             np.save(os.path.join(out_dir, "peaks.npy"), all_pk)
             np.save(os.path.join(out_dir, "peak_counts.npy"), all_ct)
@@ -108,4 +145,4 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:3])
+    main(*sys.argv[1:3], label_dir=sys.argv[3] if len(sys.argv) > 3 else None)

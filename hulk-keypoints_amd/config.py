@@ -23,7 +23,14 @@ files may hold [K,2], [K,3] or [K,m,3] (u, v, flag) with m <= M, a keypoint clas
 have several instances or none, points outside the image are marked absent instead
 of clipped, and the loss runs against the maximum of the instances' Gaussians,
 hkp_heat_loss_multi) and ABSENT ("zero": a keypoint that is not in the picture is
-trained against the all-zero heatmap; "ignore": its plane is left out of the loss).
+trained against the all-zero heatmap; "ignore": its plane is left out of the loss),
+EVAL (None: train.py and analysis.py report what the reference reports; a dict such as
+{"thresholds": (2, 4, 8, 16), "max_peaks": 4, "radius": 1, "threshold": 0.1} — also
+"bins" —: the test loop of train.py's fit() decodes the peaks of its one forward per
+batch, matches them to the labels on the GPU (hkp.metrics.KeypointMetrics) and prints
+one more line after `test loss:` with the recall per distance threshold (pixels), the
+mAP and the mean localisation error; analysis.py, given a label directory, writes
+preds/metrics.json).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -44,3 +51,4 @@ RESIZE_PARAMS = {}
 PEAKS = None
 INSTANCES = None
 ABSENT = "zero"
+EVAL = None

@@ -192,6 +192,9 @@ SIGNATURES = {
     "hkp_gauss_target_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
     "hkp_heat_loss_multi_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "hkp_heat_loss_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P, _P]),
+    # evaluation: peaks/counts of hkp_heat_peaks against pts (thresholds: float array on the host)
+    "hkp_peaks_match": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_F), _P, _P, _P, _P, _P, _P,
+                                       _P, _P, _P]),
     "hkp_head_bwd_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "hkp_head_bwd": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "hkp_head_fc_bwd_workspace": (_I64, [_I32, _I32, _I32, _I32]),

@@ -1454,6 +1454,74 @@ def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=T
     return loss, dheat
 
 
+PEAKS_MATCH_MAX_T = 8                 # thresholds of one hkp_peaks_match launch
+PEAKS_MATCH_MAX_BINS = 4096           # score bins
+
+
+def match_thresholds(thresholds):
+    """The thresholds of hkp_peaks_match as a tuple of floats, validated as the kernel
+    validates them (on their fp32 values): 1 to 8, finite, > 0, strictly ascending."""
+    try:
+        th = tuple(float(v) for v in thresholds)
+    except TypeError:
+        raise ValueError("thresholds: expected a sequence of numbers, got %r" % (thresholds,))
+    f32 = [ctypes.c_float(v).value for v in th]
+    if not 1 <= len(th) <= PEAKS_MATCH_MAX_T:
+        raise ValueError("thresholds: need 1 to %d of them, got %d" % (PEAKS_MATCH_MAX_T, len(th)))
+    for q, v in enumerate(f32):
+        if not (v > 0.0 and v != float("inf")) or (q and not v > f32[q - 1]):
+            raise ValueError("thresholds: must be finite, > 0 and strictly ascending (as fp32), got %r" % (th,))
+    return th
+
+
+def peaks_match(peaks, counts, pts, thresholds, hist, totals, bins=1024, outputs=False):
+    """Match decoded peaks to labels and ADD the outcome into the accumulators
+    (hkp_peaks_match, include/hulkkp.h: COCO's greedy matching per plane and
+    threshold on squared fp64 distances).  peaks float32 [N,K,P,3] (x, y, score)
+    and counts int32 [N,K] as heat_peaks returns them; pts float32 [N,K,M,3] (u, v,
+    flag), or [N,K,2] (one present instance per plane); thresholds: 1 to 8 pixel
+    distances, ascending; hist int64 [K,T,2,bins] and totals int64 [K,8] on the
+    same device, added to in place.  One launch, no synchronisation.
+    outputs=True returns (peak_match int32 [N,K,T,P], gt_match int32 [N,K,M],
+    gt_dist float32 [N,K,M]); otherwise None."""
+    th = match_thresholds(thresholds)
+    bins = int(bins)
+    if not 1 <= bins <= PEAKS_MATCH_MAX_BINS:
+        raise ValueError("peaks_match: need 1 <= bins <= %d, got %d" % (PEAKS_MATCH_MAX_BINS, bins))
+    _need(peaks, torch.float32, "peaks_match.peaks", 4)
+    n, k, p, _ = peaks.shape
+    if peaks.shape[3] != 3 or not 1 <= p <= 16 or n < 1 or k < 1:
+        raise HkpError("peaks_match: peaks must be [N,K,P,3] with 1 <= P <= 16, got %s" % (tuple(peaks.shape),))
+    _need(counts, torch.int32, "peaks_match.counts", 2)
+    if isinstance(pts, torch.Tensor) and pts.dim() == 3:
+        _need(pts, torch.float32, "peaks_match.pts", 3)
+        if pts.shape[2] != 2:
+            raise HkpError("peaks_match: labels must be [N,K,2] or [N,K,M,3], got %s" % (tuple(pts.shape),))
+        pts = torch.cat([pts, torch.ones_like(pts[..., :1])], dim=2).unsqueeze(2).contiguous()
+    _need_pts(pts, "peaks_match.pts")
+    m = pts.shape[2]
+    t = len(th)
+    _need(hist, torch.int64, "peaks_match.hist", 4)
+    _need(totals, torch.int64, "peaks_match.totals", 2)
+    if tuple(counts.shape) != (n, k) or tuple(pts.shape[:2]) != (n, k):
+        raise HkpError("peaks_match: counts %s and pts %s do not go with peaks %s"
+                       % (tuple(counts.shape), tuple(pts.shape), tuple(peaks.shape)))
+    if tuple(hist.shape) != (k, t, 2, bins) or tuple(totals.shape) != (k, 8):
+        raise HkpError("peaks_match: need hist %s and totals %s, got %s and %s"
+                       % ((k, t, 2, bins), (k, 8), tuple(hist.shape), tuple(totals.shape)))
+    for name, x in (("counts", counts), ("pts", pts), ("hist", hist), ("totals", totals)):
+        if x.device != peaks.device:
+            raise HkpError("peaks_match: %s is on %s, peaks on %s" % (name, x.device, peaks.device))
+    pm = gm = gd = None
+    if outputs:
+        pm = torch.empty((n, k, t, p), device=peaks.device, dtype=torch.int32)
+        gm = torch.empty((n, k, m), device=peaks.device, dtype=torch.int32)
+        gd = torch.empty((n, k, m), device=peaks.device, dtype=torch.float32)
+    call("hkp_peaks_match", n, k, p, m, t, bins, (ctypes.c_float * t)(*th), _ptr(peaks), _ptr(counts), _ptr(pts),
+         _ptr(hist), _ptr(totals), _ptr(pm), _ptr(gm), _ptr(gd), _stream())
+    return (pm, gm, gd) if outputs else None
+
+
 def head_bwd(dheat, heat, h, w):
     """dlow [N,K,h,w] = upsample-adjoint(dheat * (1-heat) * heat)."""
     _need(dheat, torch.float32, "head_bwd.dheat", 4)

@@ -251,6 +251,22 @@ def predict_peaks_dp(model, x_shard, max_peaks=4, radius=1, threshold=0.0, sync=
     return gather_peaks(peaks, counts, group)
 
 
+@torch.no_grad()
+def evaluate_dp(model, x_shard, labels_shard, metrics, max_peaks=4, radius=1, threshold=0.0, sync=False, group=None,
+                global_batch=None):
+    """Each rank's shard through the fused forward, the multi-peak decode and the
+    on-device matching against its own labels (KeypointsGauss.evaluate), added into
+    this rank's `metrics` (hkp.metrics.KeypointMetrics).  No collective per batch:
+    nothing is gathered; the caller sums the ranks' integer accumulators once, at the
+    end of the pass, with metrics.all_reduce(group).  sync / group / global_batch: as
+    for predict_peaks_dp.  Returns this shard's (peaks, counts)."""
+    pol = model.policy.with_(sync_bn=True, sync_group=group) if sync else model.policy
+    if sync:
+        ShardCheck(group)(x_shard.shape[0], global_batch)
+    return model.evaluate(x_shard, labels_shard, metrics, max_peaks=max_peaks, radius=radius, threshold=threshold,
+                          policy=pol)
+
+
 # ---- SyncBN (SURVEY §8(e), caveat D5) ----------------------------------------
 # Off by default: per-rank BN statistics (standard DDP semantics, as above).  On
 # (Policy(sync_bn=True, sync_group=...), carried by the model or the Trainer):

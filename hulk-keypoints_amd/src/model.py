@@ -77,6 +77,16 @@ class KeypointsGauss(nn.Module):
         return ops.heat_peaks(low, H, W, max_peaks=max_peaks, radius=radius, threshold=threshold)
 
     @torch.no_grad()
+    def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None):
+        """predict_peaks, then one launch that matches the peaks to `labels` ([B,K,M,3]
+        (u, v, flag) or [B,K,2], in input pixels, on the device) and adds the outcome
+        into `metrics` (hkp.metrics.KeypointMetrics); no host synchronisation.
+        Returns the (peaks, counts) of predict_peaks."""
+        peaks, counts = self.predict_peaks(x, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=policy)
+        metrics.update(peaks, counts, labels)
+        return peaks, counts
+
+    @torch.no_grad()
     def heatmaps_and_keypoints(self, x, policy=None):
         hm, yx, _ = net.keypoints_forward(self.resnet.net, x, self.num_keypoints, heat=True, argmax=True,
                                           pol=policy or self.policy)

@@ -47,6 +47,12 @@ class Prediction:
         keypoints().  kw: max_peaks, radius, threshold (KeypointsGauss.predict_peaks)."""
         return self.model.predict_peaks(self._batch(imgs), **kw)
 
+    def evaluate(self, imgs, labels, metrics, **kw):
+        """peaks(), matched on the GPU to `labels` ([B,K,M,3] (u, v, flag) or [B,K,2]) and
+        added into `metrics` (hkp.metrics.KeypointMetrics); kw as for peaks().  Returns
+        what peaks() returns (KeypointsGauss.evaluate)."""
+        return self.model.evaluate(self._batch(imgs), labels, metrics, **kw)
+
     def softmax(self, x):
         e_x = np.exp(x - np.max(x))
         return e_x / e_x.sum()

@@ -12,6 +12,12 @@ buckets overlapped with the backward kernels: the model's grad_ready hook hands
 each gradient to hkp.train.GradBucketer as the backward produces it inside
 loss.backward(), a full bucket's all-reduce starts right away, and
 _reduce_grads only waits for the last ones.  Rank 0 prints and checkpoints.
+
+With config.EVAL set (default None: nothing changes) the test loop makes one forward
+per batch under no_grad, takes the test loss from its heatmaps and the decoded peaks
+from its low-res logits, matches them to the labels on the GPU
+(hkp.metrics.KeypointMetrics) and prints one more line, `test eval: ...`, after
+`test loss:`.  Every rank walks the whole test set, so no reduction is needed.
 """
 import os
 import sys
@@ -21,10 +27,11 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
+from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, EVAL, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
                     GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS,
                     batch_size, epochs)
 from hkp import autograd as hkp_autograd
+from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
 from src.dataset import KeypointsDataset, domain_randomization, transform
 from src.model import KeypointsGauss
@@ -42,7 +49,10 @@ def _rank0():
 def forward(sample_batched, model):
     img, gt = sample_batched
     img = img.cuda(non_blocking=True)
-    pred_gauss = model.forward(img)
+    return _loss(model.forward(img), gt)
+
+
+def _loss(pred_gauss, gt):
     if gt.dim() == 3:   # (u, v) labels → the loss kernel recomputes the Gaussian target in registers
         return hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS)
     if gt.dim() == 4 and gt.shape != pred_gauss.shape and gt.shape[-1] == 3 and gt.is_floating_point():
@@ -50,6 +60,28 @@ def forward(sample_batched, model):
         return hkp_autograd.heatmap_loss(pred_gauss, pts=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
                                          absent=ABSENT)
     return hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS)
+
+
+def eval_forward(sample_batched, model, metrics, peak_kw):
+    """The test step with config.EVAL set: ONE forward under no_grad gives the test
+    loss (from its heatmaps) and, from its low-res logits, the decoded peaks, which one
+    more launch matches to the batch's labels and adds into `metrics`
+    (hkp.metrics.KeypointMetrics); no host synchronisation beyond the caller's
+    loss.item().  The labels must be (u, v) [B,K,2] or instances [B,K,M,3]."""
+    img, gt = sample_batched
+    dense = (img.shape[0], model.num_keypoints) + tuple(net.image_nchw_shape(img)[2:])
+    if tuple(gt.shape) == dense or not (gt.dim() == 3 or (gt.dim() == 4 and gt.shape[-1] == 3)):
+        raise ops.HkpError("EVAL needs point labels ([B,K,2] or [B,K,M,3]), not dense targets %s: build the test "
+                           "set with return_uv=True" % (tuple(gt.shape),))
+    img = img.cuda(non_blocking=True)
+    with torch.no_grad():
+        heat, _, low = net.keypoints_forward(model.resnet.net, img, model.num_keypoints, heat=True, argmax=False,
+                                             pol=model.policy)
+        loss = _loss(heat, gt)
+        H, W = net.image_nchw_shape(img)[2:]
+        peaks, counts = ops.heat_peaks(low, H, W, **peak_kw)
+        metrics.update(peaks, counts, gt.cuda().float().contiguous())
+    return loss
 
 
 def _reduce_grads(model):
@@ -73,6 +105,10 @@ def setup_data_parallel(model, bucket_mb=32):
 
 
 def fit(train_data, test_data, model, epochs, checkpoint_path=""):
+    metrics = peak_kw = None
+    if EVAL is not None:            # every rank walks the whole test set: no reduction needed
+        from hkp.metrics import from_config
+        metrics, peak_kw = from_config(EVAL, model.num_keypoints)
     for epoch in range(epochs):
         if hasattr(getattr(train_data, "sampler", None), "set_epoch"):
             train_data.sampler.set_epoch(epoch)
@@ -94,11 +130,18 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
             print("train loss:", train_loss / max(i_batch, 1))   # reference divides by i_batch (train.py:40)
         test_loss = 0.0
         i_batch = 0
+        if metrics is not None:
+            metrics.reset()
         for i_batch, sample_batched in enumerate(test_data):
-            loss = forward(sample_batched, model)
+            if metrics is None:
+                loss = forward(sample_batched, model)
+            else:
+                loss = eval_forward(sample_batched, model, metrics, peak_kw)
             test_loss += loss.item()
         if _rank0():
             print("test loss:", test_loss / max(i_batch, 1))
+            if metrics is not None:
+                print("test eval:", metrics.summary())
             if epoch % 2 == 0:
                 torch.save(model.state_dict(), checkpoint_path + "/model_2_1_" + str(epoch) + ".pth")
 

@@ -714,6 +714,56 @@ int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, i
                         const float* heat, const float* pts, float sigma, double* loss, float* dheat, void* workspace,
                         hkp_stream_t stream);
 
+/* Keypoint evaluation (not in the reference): the peaks and counts of
+ * hkp_heat_peaks, peaks [n][k][p][3] (x, y, score) and counts [n][k], matched
+ * plane by plane to the labels of hkp_heat_loss_multi, pts [n][k][m][3] (u, v,
+ * flag), at t distance thresholds at once, and ADDED into two int64 accumulators
+ * that stay on the device: hist [k][t][2][bins] and totals [k][8].  One launch,
+ * no host synchronisation.  thresholds_host [t] is host memory and is passed to
+ * the kernel by value; thresholds are in pixels of the frame of peaks and labels.
+ * Per plane (b, c):
+ *  slots:     cnt = clamp(counts[b][c], 0, p); peak slots at index cnt and above
+ *             are never read, whatever they hold.  A label slot is present iff
+ *             flag > 0 (hkp_heat_loss_multi's rule); the (u, v) of an empty slot
+ *             are never read into the result.
+ *  distance:  dx = (double)x - (double)u, dy likewise, d2 = dx*dx + dy*dy in fp64
+ *             without fused multiply-add.  Every decision is made on d2: within
+ *             threshold tau means d2 <= (double)tau * (double)tau, inclusive, so a
+ *             NaN coordinate never matches (such a peak is a false positive, such
+ *             a present instance a miss).  No square root takes part in a decision.
+ *  matching:  independently per threshold index ti, COCO's greedy rule: the peaks
+ *             in slot order 0 .. cnt-1 (best first, as hkp_heat_peaks writes them)
+ *             each take the nearest present instance that is not yet taken at this
+ *             threshold and lies within tau[ti]; equal d2 goes to the lower label
+ *             slot.  A peak that takes one is a true positive, else a false
+ *             positive.
+ *  score bin: in fp32, bin = s >= 1 ? bins-1 : !(s > 0) ? 0 :
+ *             min(bins-1, (int)(s * (float)bins)); NaN goes to bin 0.
+ *             hist[c][ti][0][bin] += 1 for a true positive, hist[c][ti][1][bin] += 1
+ *             for a false positive.
+ *  totals[c]: [0] planes seen, [1] planes without a present slot (absent
+ *             keypoints), [2] present instances, [3] peaks (sum of cnt),
+ *             [4] instances matched at the loosest threshold t-1, [5] the sum over
+ *             those matches of (int64)floor((double)dist32 * 65536.0 + 0.5) with
+ *             dist32 = (float)sqrt(d2), the very value written to gt_dist,
+ *             [6] peaks on absent planes, [7] is never touched.
+ *  per batch (each skipped when NULL):
+ *             peak_match [n][k][t][p] int32: the label slot taken, -1 for an
+ *             unmatched peak, -2 for a slot j >= cnt;
+ *             gt_match [n][k][m] int32: at the loosest threshold the peak slot that
+ *             took instance i, -1 for a present but missed instance, -2 for an
+ *             empty slot; gt_dist [n][k][m] fp32: the distance of that match,
+ *             else -1.
+ * Everything accumulated is an integer (64-bit integer atomic adds, the totals
+ * combined per block first), so the result does not depend on the order of the
+ * additions: the same inputs give the same bits.  Limits: n, k >= 1,
+ * 1 <= p, m <= 16, 1 <= t <= 8, 1 <= bins <= 4096, thresholds finite, > 0 and
+ * strictly ascending; anything else is HKP_ERR_BAD_ARG with no launch. */
+int hkp_peaks_match(int32_t n, int32_t k, int32_t p, int32_t m, int32_t t, int32_t bins,
+                    const float* thresholds_host, const float* peaks, const int32_t* counts, const float* pts,
+                    int64_t* hist, int64_t* totals, int32_t* peak_match, int32_t* gt_match, float* gt_dist,
+                    hkp_stream_t stream);
+
 /* dlow = upsample-adjoint( dheat * (1-heat) * heat ) (sigmoid backward fused;
  * heat NULL = dheat is already the pre-sigmoid gradient): a row gather into
  * `workspace` (hkp_head_bwd_workspace bytes: [n*k][H][w] floats), then a column
