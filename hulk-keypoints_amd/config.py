@@ -30,7 +30,12 @@ EVAL (None: train.py and analysis.py report what the reference reports; a dict s
 batch, matches them to the labels on the GPU (hkp.metrics.KeypointMetrics) and prints
 one more line after `test loss:` with the recall per distance threshold (pixels), the
 mAP and the mean localisation error; analysis.py, given a label directory, writes
-preds/metrics.json).
+preds/metrics.json), MAX_GRAD_NORM (None: the reference's bare Adam step; a float > 0:
+train.py's optimizer is hkp.optim.FusedAdam and clips the gradients by their global L2
+norm to that value before each step, on the GPU) and EMA_DECAY (None; a float strictly
+between 0.5 and 1: FusedAdam also keeps an exponential moving average of the parameters,
+fit() runs its test loop on it and writes model_2_1_<epoch>_ema.pth next to each
+checkpoint).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -52,3 +57,5 @@ PEAKS = None
 INSTANCES = None
 ABSENT = "zero"
 EVAL = None
+MAX_GRAD_NORM = None
+EMA_DECAY = None

@@ -174,6 +174,11 @@ SIGNATURES = {
     "hkp_conv_bwd_filter_x3_workspace": (_I64, [_CD]),
     "hkp_conv2d_bwd_filter_x3": (ctypes.c_int, [_CD, _P, _P, _P, _P, _P, _I64, _P]),
     "hkp_adam_step": (ctypes.c_int, [_I32, ctypes.POINTER(AdamTensor), _F, _F, _F, _F, _F, _F, _F, _P]),
+    # gradient clipping / weight EMA (ema: host array of device pointers; coef, partials, out: device)
+    "hkp_grad_norm_partials": (_I64, [_I32, ctypes.POINTER(AdamTensor)]),
+    "hkp_grad_norm": (ctypes.c_int, [_I32, ctypes.POINTER(AdamTensor), _F, _P, _I64, _P, _P]),
+    "hkp_adam_step_ex": (ctypes.c_int, [_I32, ctypes.POINTER(AdamTensor), ctypes.POINTER(_P), _F, _P, _F, _F, _F, _F,
+                                        _F, _F, _F, _P]),
     # backward
     "hkp_conv_weight_flip":(ctypes.c_int, [_CD, _P, _P, _P]),
     "hkp_conv2d_bwd_data": (ctypes.c_int, [_CD, _P, _P, _P, _P, _P]),

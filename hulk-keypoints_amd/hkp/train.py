@@ -130,8 +130,14 @@ class Trainer:
     """One optimizer step per call, reference semantics (train.py:33-36)."""
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-4, loss="bce", sigma=8.0, distributed=False,
-                 bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False, absent="zero"):
-        """absent: what a plane of multi-instance labels (pts [B,K,M,3]: u, v, flag) without
+                 bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False, absent="zero",
+                 max_grad_norm=None, ema_decay=None):
+        """max_grad_norm / ema_decay: FusedAdam's options (hkp.optim): clip the gradients
+        by their global L2 norm; keep an exponential moving average of the parameters
+        (ema_weights() runs a block on it).  Under data parallelism the norm is taken in
+        opt.step(), after the bucketed all-reduce: every rank holds the same averaged
+        gradients and computes the same coefficient, with no further collective.
+        absent: what a plane of multi-instance labels (pts [B,K,M,3]: u, v, flag) without
         a present instance does: "zero" trains it against the all-zero target, "ignore"
         leaves it out of the loss (its gradient is zero, the mean runs over the other
         planes).  Under data parallelism "ignore" divides by each rank's own count of
@@ -166,8 +172,13 @@ class Trainer:
         self.absent = absent
         if optimizer not in ("fused", "torch"):
             raise ValueError("optimizer must be 'fused' or 'torch'")
-        opt_cls = FusedAdam if optimizer == "fused" else torch.optim.Adam
-        self.opt = opt_cls(self.params, lr=lr, weight_decay=weight_decay)
+        if optimizer == "fused":
+            self.opt = FusedAdam(self.params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                 ema_decay=ema_decay)
+        elif max_grad_norm is not None or ema_decay is not None:
+            raise ValueError("max_grad_norm / ema_decay need optimizer='fused'")
+        else:
+            self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay)
         use_dp = distributed and dist.is_initialized() and dist.get_world_size(group) > 1
         if use_dp:
             broadcast_state(model, group=group)   # every replica starts from rank 0's weights and BN buffers
@@ -204,3 +215,8 @@ class Trainer:
         loss = self.forward_backward(x, uv, target, global_batch, pts=pts)
         self.opt.step()
         return loss
+
+    def ema_weights(self):
+        """Context manager: the model's parameters are their EMA inside the block
+        (FusedAdam.ema_weights)."""
+        return self.opt.ema_weights()

@@ -18,7 +18,17 @@ per batch under no_grad, takes the test loss from its heatmaps and the decoded p
 from its low-res logits, matches them to the labels on the GPU
 (hkp.metrics.KeypointMetrics) and prints one more line, `test eval: ...`, after
 `test loss:`.  Every rank walks the whole test set, so no reduction is needed.
+
+With config.MAX_GRAD_NORM or config.EMA_DECAY set (default None: nothing changes) main()
+builds hkp.optim.FusedAdam with those options instead of torch's Adam: the gradients are
+clipped by their global L2 norm (after the all-reduce under data parallelism) and / or
+an exponential moving average of the parameters is kept.  With an EMA the test loop
+runs on the averaged weights (optimizer.ema_weights()), and next to each
+model_2_1_<epoch>.pth (the raw weights, needed to resume) fit() writes
+model_2_1_<epoch>_ema.pth.  The EMA covers the parameters; BN running statistics are
+buffers and are saved as they stand.
 """
+import contextlib
 import os
 import sys
 
@@ -27,9 +37,9 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, EVAL, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
-                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS,
-                    batch_size, epochs)
+from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
+                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE,
+                    RESIZE_PARAMS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
@@ -104,6 +114,14 @@ def setup_data_parallel(model, bucket_mb=32):
     return _bucketer
 
 
+def _ema_weights():
+    """optimizer.ema_weights() if the optimizer keeps an EMA (hkp.optim.FusedAdam with
+    ema_decay), else a context that does nothing."""
+    if hasattr(optimizer, "ema_weights") and any(g.get("ema_decay") is not None for g in optimizer.param_groups):
+        return optimizer.ema_weights(), True
+    return contextlib.nullcontext(), False
+
+
 def fit(train_data, test_data, model, epochs, checkpoint_path=""):
     metrics = peak_kw = None
     if EVAL is not None:            # every rank walks the whole test set: no reduction needed
@@ -132,16 +150,21 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
         i_batch = 0
         if metrics is not None:
             metrics.reset()
-        for i_batch, sample_batched in enumerate(test_data):
-            if metrics is None:
-                loss = forward(sample_batched, model)
-            else:
-                loss = eval_forward(sample_batched, model, metrics, peak_kw)
-            test_loss += loss.item()
+        ema_ctx, has_ema = _ema_weights()
+        with ema_ctx:                   # with an EMA: the test loop and the _ema checkpoint on the averaged weights
+            for i_batch, sample_batched in enumerate(test_data):
+                if metrics is None:
+                    loss = forward(sample_batched, model)
+                else:
+                    loss = eval_forward(sample_batched, model, metrics, peak_kw)
+                test_loss += loss.item()
+            if _rank0():
+                print("test loss:", test_loss / max(i_batch, 1))
+                if metrics is not None:
+                    print("test eval:", metrics.summary())
+                if has_ema and epoch % 2 == 0:
+                    torch.save(model.state_dict(), checkpoint_path + "/model_2_1_" + str(epoch) + "_ema.pth")
         if _rank0():
-            print("test loss:", test_loss / max(i_batch, 1))
-            if metrics is not None:
-                print("test eval:", metrics.summary())
             if epoch % 2 == 0:
                 torch.save(model.state_dict(), checkpoint_path + "/model_2_1_" + str(epoch) + ".pth")
 
@@ -180,7 +203,12 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
                             num_workers=workers)
     test_data = DataLoader(test_dataset, batch_size=batch_size, shuffle=True, num_workers=workers)
     keypoints = KeypointsGauss(NUM_KEYPOINTS, img_height=IMG_HEIGHT, img_width=IMG_WIDTH, backbone=BACKBONE).cuda()
-    optimizer = torch.optim.Adam(keypoints.parameters(), lr=1.0e-4, weight_decay=1.0e-4)   # train.py:79
+    if MAX_GRAD_NORM is None and EMA_DECAY is None:
+        optimizer = torch.optim.Adam(keypoints.parameters(), lr=1.0e-4, weight_decay=1.0e-4)   # train.py:79
+    else:                               # the same step with clipping and / or a weight EMA in its one pass
+        from hkp.optim import FusedAdam
+        optimizer = FusedAdam(keypoints.parameters(), lr=1.0e-4, weight_decay=1.0e-4, max_grad_norm=MAX_GRAD_NORM,
+                              ema_decay=EMA_DECAY)
     if world > 1:
         setup_data_parallel(keypoints)
     fit(train_data, test_data, keypoints, epochs=epochs, checkpoint_path=save_dir)

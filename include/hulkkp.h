@@ -662,6 +662,30 @@ int hkp_adam_step(int32_t ntensors, const hkp_adam_tensor* tensors, float beta2,
                   float one_minus_beta2, float eps, float weight_decay, float neg_step_size,
                   float bias_correction2_sqrt, hkp_stream_t stream);
 
+/* Global L2 norm of every gradient of a tensor table and the clip coefficient of
+ * clip_grad_norm_ (torch/nn/utils/clip_grad.py), both left on the device:
+ *   out[0] = norm = (float)sqrt(sum g^2),  c = max_norm / (norm + 1e-6f) in fp32,
+ *   out[1] = coef = c < 1 ? c : (c != c ? c : 1)        (torch.clamp(c, max=1.0): NaN stays NaN)
+ * Only `grad` and `n` of each entry are read.  One block per 4096-element unit
+ * squares in fp64 (exact for fp32) and sums in a fixed order (thread, wave64, the
+ * four waves) into one fp64 partial in `partials` (device, partials_len doubles,
+ * at least hkp_grad_norm_partials(ntensors, tensors)); a single block sums the
+ * partials in a fixed order.  No atomics, no host read: the same bits on every run.
+ * max_norm > 0; +inf gives the norm alone (coef = 1 for a finite norm). */
+int64_t hkp_grad_norm_partials(int32_t ntensors, const hkp_adam_tensor* tensors);
+int hkp_grad_norm(int32_t ntensors, const hkp_adam_tensor* tensors, float max_norm, double* partials,
+                  int64_t partials_len, float* out, hkp_stream_t stream);
+
+/* hkp_adam_step with two optional extras in the same pass (both NULL: hkp_adam_step):
+ *   coef (device float, e.g. out + 1 of hkp_grad_norm): g = g * coef before the
+ *     update — _foreach_mul_(grads, clip_coef) followed by Adam; g is not written;
+ *   ema ([ntensors] device pointers, one per entry of `tensors`) with
+ *     one_minus_decay in (0, 0.5): after the update e = e + one_minus_decay * (p - e),
+ *     torch._foreach_lerp_(ema, params, 1 - decay) (torch/optim/swa_utils.py). */
+int hkp_adam_step_ex(int32_t ntensors, const hkp_adam_tensor* tensors, float* const* ema, float one_minus_decay,
+                     const float* coef, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                     float weight_decay, float neg_step_size, float bias_correction2_sqrt, hkp_stream_t stream);
+
 /* Stem: backward of maxpool3x3/s2/p1(relu(y*scale+shift)) → dz = dL/d(BN output)
  * [n,h,w,c], ReLU mask applied (src/resnet.py:200-202; ATen's first-max window
  * rule): each window's dpool goes to the tap the forward recorded in `route`
