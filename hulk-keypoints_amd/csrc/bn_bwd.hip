@@ -331,8 +331,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long n4, int C4, cons
 
 // Stem maxpool(3x3,s2,p1) ∘ relu ∘ BN-affine backward, as a gather over the ≤2x2
 // pooling windows that contain each input pixel.  Emits dz = dL/d(BN output)
-// (ReLU mask applied).  Window argmax = first max in (dr, ds) scan order, NaN
-// wins — ATen's CPU max_pool2d rule.
+// (ReLU mask applied).  Window argmax = first max in (dr, ds) scan order (ATen's
+// window scan).  A NaN never wins, unlike ATen's CPU max_pool2d: the forward's
+// relu(t) = t > 0 ? t : 0 has made it 0 before the `t > m` comparison sees it.
 // dz at input pixel (h, w): the sum of dpool over the (<= 4) windows whose
 // routed tap (written by the forward, hkp_bn_relu_maxpool) is this pixel, in
 // window order (ho, wo) ascending; 0xFF routes nothing (window max <= 0: the

@@ -815,6 +815,8 @@ def bn_apply(y, ss, res=None, res_ss=None, relu=True, out=None, split=0, keep_fp
     _check_split(split, c, "bn_apply")
     if ss.numel() != 2 * c:
         raise HkpError("bn_apply: scale_shift size %d != 2C" % ss.numel())
+    if res_ss is not None and res_ss.numel() != 2 * c:
+        raise HkpError("bn_apply: res_scale_shift size %d != 2C" % res_ss.numel())
     res_sp = None
     if res is not None and res.dtype == torch.float16:
         if res_ss is not None or getattr(res, "_hkp_split_passes", 0) != 3:
