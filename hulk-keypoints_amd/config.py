@@ -1,7 +1,15 @@
 """config.py of the reference (config.py:1-6), same names and defaults.
 
 Additive keys (defaults reproduce the reference): BACKBONE, LOSS
-('bce' is what train.py:25 uses; 'mse' is train.py:13's unused MSE),
+('bce' is what train.py:25 uses; 'mse' is train.py:13's unused MSE; 'qfl' is the quality
+focal loss, not in the reference: BCE against the Gaussian target scaled per pixel by
+|target - heat|^beta, so the many easy background pixels stop dominating the sum while
+the minimum stays at heat == target, hkp_heat_loss_multi_ex; point labels only) and
+LOSS_PARAMS (the other keyword arguments of that loss: {} for 'bce' and 'mse'; for 'qfl'
+beta in [1, 8], default 2.0, and norm, "elements": the mean over the pixels, the default,
+or "instances": the sum over the pixels divided by the number of keypoint instances
+present in the batch, at least 1; "instances" also goes with 'bce' / 'mse' when INSTANCES
+is set),
 DOMAIN_RANDOMIZATION (True: the train set goes through the reference's commented-out
 augmentation pipeline, dataset.py:18-31, on the GPU) and DR_SEED (its seed),
 GEOMETRIC_AUGMENTATION (True: the train set's images and labels go through
@@ -46,6 +54,7 @@ batch_size = 4
 
 BACKBONE = "resnet34"
 LOSS = "bce"
+LOSS_PARAMS = {}
 DOMAIN_RANDOMIZATION = False
 DR_SEED = 0
 GEOMETRIC_AUGMENTATION = False

@@ -9,6 +9,12 @@
 //                    formulas, clamps and fp64 arithmetic.  Absent planes are
 //                    negatives (HKP_ABSENT_ZERO) or leave the mean (HKP_ABSENT_IGNORE:
 //                    dheat +0, divisor H*W*A with A counted on the device).
+//  * hkp_heat_loss_multi_ex  the same launch scheme with two more choices: the
+//                    quality focal kind HKP_LOSS_QFL (|t - p|^beta * BCE; beta = 2 is
+//                    its own instantiation without pow) and the divisor
+//                    HKP_NORM_INSTANCES (the present slots of the batch, counted by
+//                    the pre-kernel that counts A).  Its kernels are its own: those
+//                    of hkp_heat_loss_multi stay as they are.
 //
 // A block works on one chunk of one plane (block = plane * chunks + chunk), so
 // the plane's records are read once per block: wave 0 compacts the present
@@ -103,24 +109,36 @@ __global__ __launch_bounds__(256) void gauss_target_multi_kernel(int m, int H, i
     }
 }
 
-// inv[0] = 1 / (H*W*A), A = planes with a present slot; 0 when there is none
-__global__ __launch_bounds__(256) void multi_active_kernel(int planes, int m, double hw, const float* __restrict__ pts,
-                                                          double* __restrict__ inv) {
-    __shared__ int red[4];
-    int c = 0;
+// HKP_NORM_ELEMENTS: inv[0] = 1 / (H*W*A), A = planes with a present slot; 0 when there
+// is none.  HKP_NORM_INSTANCES: inv[0] = 1 / max(P, 1), P = present slots of all planes.
+__global__ __launch_bounds__(256) void multi_active_kernel(int planes, int m, double hw, int norm_mode,
+                                                          const float* __restrict__ pts, double* __restrict__ inv) {
+    __shared__ int red[4], redp[4];
+    int c = 0, np = 0;
     for (int p = threadIdx.x; p < planes; p += 256) {
         const float* rec = pts + (long)p * 3 * m;
-        bool any = false;
-        for (int j = 0; j < m; ++j) any = any || rec[3 * j + 2] > 0.f;
-        c += any ? 1 : 0;
+        int on = 0;
+        for (int j = 0; j < m; ++j) on += rec[3 * j + 2] > 0.f ? 1 : 0;
+        c += on > 0 ? 1 : 0;
+        np += on;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    for (int o = 32; o > 0; o >>= 1) {
+        c += __shfl_xor(c, o);
+        np += __shfl_xor(np, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = c;
+        redp[threadIdx.x >> 6] = np;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         const int a = red[0] + red[1] + red[2] + red[3];
-        inv[0] = a > 0 ? 1.0 / (hw * (double)a) : 0.0;
+        const int pres = redp[0] + redp[1] + redp[2] + redp[3];
+        if (norm_mode == HKP_NORM_INSTANCES)
+            inv[0] = 1.0 / (double)(pres > 1 ? pres : 1);
+        else
+            inv[0] = a > 0 ? 1.0 / (hw * (double)a) : 0.0;
     }
 }
 
@@ -207,6 +225,119 @@ __global__ __launch_bounds__(256) void loss_multi_finalize_kernel(int nparts, do
     if (threadIdx.x == 0) loss[0] = t * (inv_n_dev ? inv_n_dev[0] : inv_n_host);
 }
 
+// ---- hkp_heat_loss_multi_ex: the kinds of loss_elem plus the quality focal loss ----
+// QFL2: beta == 2 (d*d, no pow); QFLG: any beta in [1, 8], bm1 = beta - 1.
+constexpr int EX_BCE = 0, EX_MSE = 1, EX_QFL2 = 2, EX_QFLG = 3;
+
+template <int EK>
+__device__ __forceinline__ double loss_elem_ex(double x, double y, double inv_n, double beta, double bm1,
+                                               float* g_out) {
+    if constexpr (EK == EX_BCE) {
+        return loss_elem<HKP_LOSS_BCE>(x, y, inv_n, g_out);
+    } else if constexpr (EK == EX_MSE) {
+        return loss_elem<HKP_LOSS_MSE>(x, y, inv_n, g_out);
+    } else {
+        // float64 autograd of binary_cross_entropy(x, y, 'none') * |x - y|^beta (ATen's clamps)
+        const double bce = (y - 1.0) * fmax(log1p(-x), -100.0) - y * fmax(log(x), -100.0);
+        const double d = x - y;
+        const double den = fmax((1.0 - x) * x, (double)1e-12f);
+        double l, g;
+        if constexpr (EK == EX_QFL2) {
+            const double dd = d * d;
+            l = dd * bce;
+            g = (2.0 * d * bce + dd * d / den) * inv_n;
+        } else {
+            const double ad = fabs(d);
+            const double pm1 = pow(ad, bm1);      // |d|^(beta-1); beta = 1: exactly 1
+            const double pw = pm1 * ad;
+            l = pw * bce;
+            g = (beta * pm1 * copysign(1.0, d) * bce + pw * d / den) * inv_n;
+        }
+        // p == t: the minimum, exactly (0^0 at beta = 1, the clamped logs at 0 and 1)
+        if (d == 0.0) {
+            l = 0.0;
+            g = 0.0;
+        }
+        *g_out = (float)g;
+        return l;
+    }
+}
+
+// heat_loss_multi_kernel with the kind EK, leaving absent planes out on `ignore` and
+// reading the divisor from inv_n_dev whenever it is set (either may come without the other)
+template <int EK, bool VEC4>
+__global__ __launch_bounds__(256) void heat_loss_multi_ex_kernel(int m, int H, int W, int chunks, float den, int ignore,
+                                                                float betaf, double inv_n_host,
+                                                                const double* __restrict__ inv_n_dev,
+                                                                const float* __restrict__ p,
+                                                                const float* __restrict__ pts,
+                                                                float* __restrict__ dheat, double* __restrict__ part) {
+    __shared__ float su[MULTI_MAX_M], sv[MULTI_MAX_M];
+    __shared__ int scnt;
+    __shared__ double red[4];
+    const long plane = blockIdx.x / chunks;
+    const int chunk = blockIdx.x - (int)plane * chunks;
+    const int cnt = stage_instances(pts + plane * 3 * m, m, su, sv, &scnt);
+    const int HW = H * W;
+    const float* pp = p + plane * (long)HW;
+    float* dp = dheat ? dheat + plane * (long)HW : nullptr;
+    const int first = chunk * 256 + threadIdx.x, step = chunks * 256;
+    if (ignore && cnt == 0) {
+        if (dp) {
+            if constexpr (VEC4) {
+                for (int q = first; q < (HW >> 2); q += step) ((f32x4*)dp)[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                for (int i = first; i < HW; i += step) dp[i] = 0.f;
+            }
+        }
+        if (threadIdx.x == 0) part[blockIdx.x] = 0.0;
+        return;
+    }
+    const double inv_n = inv_n_dev ? inv_n_dev[0] : inv_n_host;
+    const double beta = (double)betaf, bm1 = beta - 1.0;
+    double acc = 0.0;
+    if constexpr (VEC4) {
+        const int W4 = W >> 2;
+        for (int q = first; q < (HW >> 2); q += step) {
+            const int yy = q / W4, x0 = (q - yy * W4) * 4;
+            const f32x4 xv = ((const f32x4*)pp)[q];
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < cnt; ++j) {
+                const float u = su[j];
+                const float dy = (float)yy - sv[j];
+                const float dy2 = dy * dy;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float dx = (float)(x0 + e) - u;
+                    t[e] = fmaxf(t[e], expf(-(dx * dx + dy2) / den));
+                }
+            }
+            f32x4 gv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float g;
+                acc += loss_elem_ex<EK>((double)xv[e], (double)t[e], inv_n, beta, bm1, &g);
+                gv[e] = g;
+            }
+            if (dp) ((f32x4*)dp)[q] = gv;
+        }
+    } else {
+        for (int i = first; i < HW; i += step) {
+            const int yy = i / W, xx = i - yy * W;
+            float t = 0.f;
+            for (int j = 0; j < cnt; ++j) {
+                const float dx = (float)xx - su[j], dy = (float)yy - sv[j];
+                t = fmaxf(t, expf(-(dx * dx + dy * dy) / den));
+            }
+            float g;
+            acc += loss_elem_ex<EK>((double)pp[i], (double)t, inv_n, beta, bm1, &g);
+            if (dp) dp[i] = g;
+        }
+    }
+    const double s = multi_block_sum_d(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
 static inline bool multi_sizes_ok(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W) {
     // a plane is indexed with 32-bit integers, the block index too
     return n > 0 && k > 0 && m >= 1 && m <= MULTI_MAX_M && H > 0 && W > 0 && (long)H * W <= (1L << 30) &&
@@ -256,7 +387,8 @@ extern "C" int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, i
     const int nblocks = planes * chunks;
     hipStream_t st = as_stream(stream);
     if (inv_dev) {
-        hipLaunchKernelGGL(multi_active_kernel, dim3(1), dim3(256), 0, st, planes, m, (double)HW, pts, inv_dev);
+        hipLaunchKernelGGL(multi_active_kernel, dim3(1), dim3(256), 0, st, planes, m, (double)HW,
+                           HKP_NORM_ELEMENTS, pts, inv_dev);
         HKP_LAUNCH_CHECK("hkp_heat_loss_multi(active)");
     }
 #define HKP_LOSS_M(KD, V4)                                                                                         \
@@ -271,5 +403,59 @@ extern "C" int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, i
     HKP_LAUNCH_CHECK("hkp_heat_loss_multi");
     hipLaunchKernelGGL(loss_multi_finalize_kernel, dim3(1), dim3(256), 0, st, nblocks, inv_n, inv_dev, part, loss);
     HKP_LAUNCH_CHECK("hkp_heat_loss_multi(finalize)");
+    return HKP_OK;
+}
+
+extern "C" int hkp_heat_loss_multi_ex(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                                      int32_t absent_mode, int32_t norm_mode, float beta, const float* heat,
+                                      const float* pts, float sigma, double* loss, float* dheat, void* workspace,
+                                      hkp_stream_t stream) {
+    HKP_CHECK_ARG(multi_sizes_ok(n, k, m, H, W) && sigma > 0.f,
+                  "hkp_heat_loss_multi_ex: bad sizes (1 <= m <= 16, H*W <= 2^30)");
+    HKP_CHECK_ARG(heat && pts && loss && workspace, "hkp_heat_loss_multi_ex: null tensor");
+    HKP_CHECK_ARG(loss_kind == HKP_LOSS_BCE || loss_kind == HKP_LOSS_MSE || loss_kind == HKP_LOSS_QFL,
+                  "hkp_heat_loss_multi_ex: bad loss kind");
+    HKP_CHECK_ARG(absent_mode == HKP_ABSENT_ZERO || absent_mode == HKP_ABSENT_IGNORE,
+                  "hkp_heat_loss_multi_ex: bad absent mode");
+    HKP_CHECK_ARG(norm_mode == HKP_NORM_ELEMENTS || norm_mode == HKP_NORM_INSTANCES,
+                  "hkp_heat_loss_multi_ex: bad norm mode");
+    // NaN fails both comparisons
+    HKP_CHECK_ARG(loss_kind != HKP_LOSS_QFL || (beta >= 1.f && beta <= 8.f),
+                  "hkp_heat_loss_multi_ex: beta %g outside [1, 8]", (double)beta);
+    const int planes = n * k;
+    const long HW = (long)H * W;
+    const float den = (float)(2.0 * (double)sigma * (double)sigma);
+    const bool vec4 = W % 4 == 0 && ((uintptr_t)heat & 15) == 0 && ((uintptr_t)dheat & 15) == 0;
+    const int chunks = multi_chunks(vec4 ? HW / 4 : HW);
+    const int ignore = absent_mode == HKP_ABSENT_IGNORE ? 1 : 0;
+    // the divisor comes from the device unless it is the plain n*k*H*W
+    double* inv_dev = (ignore || norm_mode == HKP_NORM_INSTANCES) ? (double*)workspace : nullptr;
+    double* part = (double*)workspace + 1;
+    const double inv_n = 1.0 / (double)((long)planes * HW);
+    const int nblocks = planes * chunks;
+    hipStream_t st = as_stream(stream);
+    if (inv_dev) {
+        hipLaunchKernelGGL(multi_active_kernel, dim3(1), dim3(256), 0, st, planes, m, (double)HW, norm_mode, pts,
+                           inv_dev);
+        HKP_LAUNCH_CHECK("hkp_heat_loss_multi_ex(active)");
+    }
+    const int ek = loss_kind == HKP_LOSS_BCE ? EX_BCE : loss_kind == HKP_LOSS_MSE ? EX_MSE
+                 : beta == 2.f ? EX_QFL2 : EX_QFLG;
+#define HKP_LOSS_EX(EK, V4)                                                                                     \
+    hipLaunchKernelGGL((heat_loss_multi_ex_kernel<EK, V4>), dim3((unsigned)nblocks), dim3(256), 0, st, m, H, W, \
+                       chunks, den, ignore, beta, inv_n, inv_dev, heat, pts, dheat, part)
+#define HKP_LOSS_EX_V(EK) \
+    if (vec4) HKP_LOSS_EX(EK, true); else HKP_LOSS_EX(EK, false)
+    switch (ek) {
+        case EX_BCE: HKP_LOSS_EX_V(EX_BCE); break;
+        case EX_MSE: HKP_LOSS_EX_V(EX_MSE); break;
+        case EX_QFL2: HKP_LOSS_EX_V(EX_QFL2); break;
+        default: HKP_LOSS_EX_V(EX_QFLG); break;
+    }
+#undef HKP_LOSS_EX_V
+#undef HKP_LOSS_EX
+    HKP_LAUNCH_CHECK("hkp_heat_loss_multi_ex");
+    hipLaunchKernelGGL(loss_multi_finalize_kernel, dim3(1), dim3(256), 0, st, nblocks, inv_n, inv_dev, part, loss);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_multi_ex(finalize)");
     return HKP_OK;
 }

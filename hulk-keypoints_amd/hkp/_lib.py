@@ -15,8 +15,12 @@ HKP_LAYOUT_NHWC = 0
 HKP_LAYOUT_NCHW = 1
 HKP_LOSS_BCE = 0
 HKP_LOSS_MSE = 1
+HKP_LOSS_QFL = 2                   # hkp_heat_loss_multi_ex only
 HKP_ABSENT_ZERO = 0
 HKP_ABSENT_IGNORE = 1
+HKP_NORM_ELEMENTS = 0
+HKP_NORM_INSTANCES = 1
+QFL_BETA_RANGE = (1.0, 8.0)        # hkp_heat_loss_multi_ex's beta, both ends included
 MAX_INSTANCES = 16                 # slots per plane of the multi-instance labels (hkp_heat_peaks' max_peaks limit)
 
 
@@ -197,6 +201,9 @@ SIGNATURES = {
     "hkp_gauss_target_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
     "hkp_heat_loss_multi_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "hkp_heat_loss_multi": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F, _P, _P, _P, _P]),
+    # ... with the quality focal kind and the divisor's choice (norm_mode, beta after absent_mode)
+    "hkp_heat_loss_multi_ex": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _F, _P, _P,
+                                              _P, _P]),
     # evaluation: peaks/counts of hkp_heat_peaks against pts (thresholds: float array on the host)
     "hkp_peaks_match": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_F), _P, _P, _P, _P, _P, _P,
                                        _P, _P, _P]),

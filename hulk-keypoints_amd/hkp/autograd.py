@@ -6,7 +6,8 @@ every parameter gradient at once.  This is what makes the reference's
 training idiom (train.py:21,25,35: ``model.forward(img).double()`` →
 ``nn.BCELoss()`` → ``loss.backward()``) work unchanged on this path.
 
-HeatmapLoss is the fused fp64 BCE/MSE (train.py:25 / :13) as a Function too.
+HeatmapLoss is the fused fp64 BCE/MSE (train.py:25 / :13) as a Function too, and the
+quality focal loss (kind="qfl", not in the reference) goes the same way.
 """
 import torch
 
@@ -39,45 +40,57 @@ def keypoints_heatmaps(model, x):
     return _KeypointsFn.apply(x, model, *model.parameters())
 
 
+def _loss_extras(kind, beta, norm):
+    """beta / norm as keyword arguments for ops, none at all for the reference's losses
+    with their defaults (those calls stay what they were)."""
+    return {"beta": beta, "norm": norm} if (kind == "qfl" or norm != "elements") else {}
+
+
 class _HeatLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, heat, target, uv, sigma, kind):
+    def forward(ctx, heat, target, uv, sigma, kind, beta, norm):
         loss, dheat = ops.heat_loss(heat.contiguous(), target, uv, sigma, kind,
-                                    want_grad=torch.is_grad_enabled() or heat.requires_grad)
+                                    want_grad=torch.is_grad_enabled() or heat.requires_grad,
+                                    **_loss_extras(kind, beta, norm))
         ctx.save_for_backward(dheat)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dheat,) = ctx.saved_tensors
-        return dheat * g.to(dheat.dtype), None, None, None, None
+        return dheat * g.to(dheat.dtype), None, None, None, None, None, None
 
 
 class _HeatLossMultiFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, heat, pts, sigma, kind, absent):
+    def forward(ctx, heat, pts, sigma, kind, absent, beta, norm):
         loss, dheat = ops.heat_loss_multi(heat.contiguous(), pts, sigma, kind, absent,
-                                          want_grad=torch.is_grad_enabled() or heat.requires_grad)
+                                          want_grad=torch.is_grad_enabled() or heat.requires_grad,
+                                          **_loss_extras(kind, beta, norm))
         ctx.save_for_backward(dheat)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dheat,) = ctx.saved_tensors
-        return dheat * g.to(dheat.dtype), None, None, None, None
+        return dheat * g.to(dheat.dtype), None, None, None, None, None, None
 
 
-def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero"):
+def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero", beta=2.0,
+                 norm="elements"):
     """mean BCE (default) or MSE between fp32 heatmaps and the fp64 Gaussian target
     (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor.
     ``pts`` [N,K,M,3] (u, v, flag) in place of both: the multi-instance target
     (ops.heat_loss_multi), planes without a present instance handled per ``absent``
-    ("zero": negatives; "ignore": left out of the mean)."""
+    ("zero": negatives; "ignore": left out of the mean).
+    ``kind="qfl"`` (``uv`` or ``pts`` labels): the quality focal loss, BCE against the
+    soft target scaled by |target - heat|^``beta`` per pixel; ``norm="instances"``
+    divides the sum by the number of present instances instead of taking the mean."""
     if pts is not None:
         if target is not None or uv is not None:
             raise ops.HkpError("heatmap_loss: pass pts alone, not with target or uv")
-        return _HeatLossMultiFn.apply(heat, pts, sigma, kind, absent)
-    return _HeatLossFn.apply(heat, target, uv, sigma, kind)
+        return _HeatLossMultiFn.apply(heat, pts, sigma, kind, absent, beta, norm)
+    return _HeatLossFn.apply(heat, target, uv, sigma, kind, beta, norm)
 
 
 class HeatmapBCELoss(torch.nn.Module):

@@ -1404,9 +1404,48 @@ def maxpool_bwd(dpool, route, in_shape):
     return dz
 
 
-def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True):
-    """fp64 BCE/MSE over [N,K,H,W] heatmaps → (loss 0-dim f64 tensor, dheat f32 or None)."""
+LOSS_KINDS = ("bce", "mse", "qfl")
+NORM_MODES = ("elements", "instances")
+ABSENT_MODES = ("zero", "ignore")
+
+
+def _loss_choice(who, kind, norm, beta):
+    """The names and beta of a loss call, checked before any tensor is looked at;
+    returns beta as the float the kernel gets (2.0 when the kind has none)."""
+    from ._lib import QFL_BETA_RANGE
+    if kind not in LOSS_KINDS:
+        raise HkpError("%s: unknown kind %r (known: %s)" % (who, kind, ", ".join(LOSS_KINDS)))
+    if norm not in NORM_MODES:
+        raise HkpError("%s: unknown norm %r (known: %s)" % (who, norm, ", ".join(NORM_MODES)))
+    if kind != "qfl":
+        return 2.0
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise HkpError("%s: beta must be a number, got %r" % (who, beta))
+    if not QFL_BETA_RANGE[0] <= b <= QFL_BETA_RANGE[1]:          # NaN fails both
+        raise HkpError("%s: beta %r outside [%g, %g]" % ((who, beta) + QFL_BETA_RANGE))
+    return b
+
+
+def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True, *, beta=2.0, norm="elements"):
+    """fp64 BCE/MSE over [N,K,H,W] heatmaps → (loss 0-dim f64 tensor, dheat f32 or None).
+    kind="qfl" (the quality focal loss of heat_loss_multi, with its beta and norm):
+    from uv labels only, each taken as one present instance; a dense target raises."""
     from ._lib import HKP_LOSS_BCE, HKP_LOSS_MSE, lib
+    if kind == "qfl" or norm != "elements":
+        _loss_choice("heat_loss", kind, norm, beta)
+        if kind != "qfl":
+            raise HkpError("heat_loss: norm %r needs kind 'qfl' or instance labels (heat_loss_multi)" % (norm,))
+        if target is not None:
+            raise HkpError("heat_loss: kind 'qfl' recomputes its target from uv; a dense target is not supported")
+        _need(heat, torch.float32, "heat_loss.heat", 4)
+        _need(uv, torch.float32, "heat_loss.uv", 3)
+        n, k = heat.shape[:2]
+        if tuple(uv.shape) != (n, k, 2):
+            raise HkpError("heat_loss: uv must be [N,K,2]")
+        pts = torch.cat([uv, torch.ones_like(uv[..., :1])], -1).reshape(n, k, 1, 3)
+        return heat_loss_multi(heat, pts, sigma, kind, "zero", want_grad, beta=beta, norm=norm)
     _need(heat, torch.float32, "heat_loss.heat", 4)
     n, k, H, W = heat.shape
     if target is not None:
@@ -1425,34 +1464,42 @@ def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True)
     return loss, dheat
 
 
-ABSENT_MODES = ("zero", "ignore")
-
-
-def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True):
+def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements"):
     """heat_loss against the multi-instance target of pts float32 [N,K,M,3] (u, v,
     flag), recomputed in registers → (loss 0-dim f64 tensor, dheat f32 or None).
     absent="zero": a plane without a present slot is trained against zeros;
     "ignore": it contributes nothing (dheat +0) and the mean runs over the other
-    planes' elements (counted on the device; none: loss 0)."""
-    from ._lib import HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, lib
+    planes' elements (counted on the device; none: loss 0).
+    kind="qfl": the quality focal loss, |t - p|^beta * BCE(p, t) per element (beta in
+    [1, 8], as a float32; its minimum is at p == t in every pixel).
+    norm="instances": the sum is divided by max(P, 1), P = the present slots of the
+    batch (counted on the device), in place of the number of elements.
+    The defaults reach hkp_heat_loss_multi; "qfl" or another norm hkp_heat_loss_multi_ex."""
+    from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
+                       HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    beta = _loss_choice("heat_loss_multi", kind, norm, beta)
+    if absent not in ABSENT_MODES:
+        raise HkpError("heat_loss_multi: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
     _need(heat, torch.float32, "heat_loss_multi.heat", 4)
     _need_pts(pts, "heat_loss_multi.pts")
     n, k, H, W = heat.shape
     if tuple(pts.shape[:2]) != (n, k) or pts.device != heat.device:
         raise HkpError("heat_loss_multi: pts %s on %s does not go with heat %s on %s"
                        % (tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
-    if kind not in ("bce", "mse"):
-        raise HkpError("heat_loss_multi: unknown kind %r (known: bce, mse)" % (kind,))
-    if absent not in ABSENT_MODES:
-        raise HkpError("heat_loss_multi: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
     if heat.numel() == 0 or not float(sigma) > 0:
         raise HkpError("heat_loss_multi: empty heat or sigma %s" % (sigma,))
     ws = torch.empty(lib().hkp_heat_loss_multi_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
     loss = torch.empty((), device=heat.device, dtype=torch.float64)
     dheat = torch.empty_like(heat) if want_grad else None
-    call("hkp_heat_loss_multi", n, k, pts.shape[2], H, W, HKP_LOSS_BCE if kind == "bce" else HKP_LOSS_MSE,
-         HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE, _ptr(heat), _ptr(pts), float(sigma), _ptr(loss),
-         _ptr(dheat), _ptr(ws), _stream())
+    kd = {"bce": HKP_LOSS_BCE, "mse": HKP_LOSS_MSE, "qfl": HKP_LOSS_QFL}[kind]
+    ab = HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE
+    if kind == "qfl" or norm != "elements":
+        call("hkp_heat_loss_multi_ex", n, k, pts.shape[2], H, W, kd, ab,
+             HKP_NORM_ELEMENTS if norm == "elements" else HKP_NORM_INSTANCES, beta, _ptr(heat), _ptr(pts),
+             float(sigma), _ptr(loss), _ptr(dheat), _ptr(ws), _stream())
+    else:
+        call("hkp_heat_loss_multi", n, k, pts.shape[2], H, W, kd, ab, _ptr(heat), _ptr(pts), float(sigma),
+             _ptr(loss), _ptr(dheat), _ptr(ws), _stream())
     return loss, dheat
 
 

@@ -131,8 +131,14 @@ class Trainer:
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-4, loss="bce", sigma=8.0, distributed=False,
                  bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False, absent="zero",
-                 max_grad_norm=None, ema_decay=None):
-        """max_grad_norm / ema_decay: FusedAdam's options (hkp.optim): clip the gradients
+                 max_grad_norm=None, ema_decay=None, loss_params=None):
+        """loss: "bce", "mse" or "qfl" (ops.LOSS_KINDS); loss_params: the other keyword
+        arguments of ops.heat_loss / ops.heat_loss_multi, e.g. {"beta": 2.0, "norm":
+        "instances"} for the quality focal loss (point labels, uv or pts, only).  Under data
+        parallelism norm="instances" divides by each rank's own count of present instances,
+        as "ignore" does with its active planes: the all-reduced gradient is the mean of the
+        per-rank quotients, not the sum over the global batch divided by its instances.
+        max_grad_norm / ema_decay: FusedAdam's options (hkp.optim): clip the gradients
         by their global L2 norm; keep an exponential moving average of the parameters
         (ema_weights() runs a block on it).  Under data parallelism the norm is taken in
         opt.step(), after the bucketed all-reduce: every rank holds the same averaged
@@ -166,6 +172,9 @@ class Trainer:
         self.policy = model.policy.with_(sync_bn=True, sync_group=self.bn_group) if sync_bn else model.policy
         self.params = list(model.parameters())
         self.loss_kind = loss
+        self.loss_params = dict(loss_params or {})
+        if set(self.loss_params) - {"beta", "norm"}:
+            raise ValueError("loss_params may hold beta and norm, got %r" % (loss_params,))
         self.sigma = sigma
         if absent not in ops.ABSENT_MODES:
             raise ValueError("absent must be one of %s, got %r" % (", ".join(ops.ABSENT_MODES), absent))
@@ -199,9 +208,11 @@ class Trainer:
         if pts is not None:
             if uv is not None or target is not None:
                 raise ops.HkpError("Trainer: pass pts alone, not with uv or target")
-            loss, dheat = ops.heat_loss_multi(hm, pts, self.sigma, self.loss_kind, self.absent, want_grad=True)
+            loss, dheat = ops.heat_loss_multi(hm, pts, self.sigma, self.loss_kind, self.absent, want_grad=True,
+                                              **self.loss_params)
         else:
-            loss, dheat = ops.heat_loss(hm, target, uv, self.sigma, self.loss_kind, want_grad=True)
+            loss, dheat = ops.heat_loss(hm, target, uv, self.sigma, self.loss_kind, want_grad=True,
+                                        **self.loss_params)
         grads = net.Grads(on_ready=self.bucketer.ready if self.bucketer else None)
         net.keypoints_backward(m.resnet.net, trace, dheat, grads)
         if self.bucketer is not None:

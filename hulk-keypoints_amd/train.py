@@ -27,6 +27,10 @@ runs on the averaged weights (optimizer.ema_weights()), and next to each
 model_2_1_<epoch>.pth (the raw weights, needed to resume) fit() writes
 model_2_1_<epoch>_ema.pth.  The EMA covers the parameters; BN running statistics are
 buffers and are saved as they stand.
+
+With config.LOSS = "qfl" (default "bce": nothing changes) the train and the test loop take
+the quality focal loss of hkp_heat_loss_multi_ex, with config.LOSS_PARAMS's beta and norm;
+it needs point labels ((u, v) or instances), which main()'s datasets give.
 """
 import contextlib
 import os
@@ -38,8 +42,8 @@ from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
 from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
-                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE,
-                    RESIZE_PARAMS, batch_size, epochs)
+                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, LOSS_PARAMS, MAX_GRAD_NORM,
+                    NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
@@ -64,12 +68,13 @@ def forward(sample_batched, model):
 
 def _loss(pred_gauss, gt):
     if gt.dim() == 3:   # (u, v) labels → the loss kernel recomputes the Gaussian target in registers
-        return hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS)
+        return hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
+                                         **LOSS_PARAMS)
     if gt.dim() == 4 and gt.shape != pred_gauss.shape and gt.shape[-1] == 3 and gt.is_floating_point():
         # instance labels [B,K,M,3] (u, v, flag): the multi-instance target, absent planes per ABSENT
         return hkp_autograd.heatmap_loss(pred_gauss, pts=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
-                                         absent=ABSENT)
-    return hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS)
+                                         absent=ABSENT, **LOSS_PARAMS)
+    return hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS, **LOSS_PARAMS)
 
 
 def eval_forward(sample_batched, model, metrics, peak_kw):

@@ -738,6 +738,34 @@ int hkp_heat_loss_multi(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, i
                         const float* heat, const float* pts, float sigma, double* loss, float* dheat, void* workspace,
                         hkp_stream_t stream);
 
+/* hkp_heat_loss_multi with a third loss kind and a choice of divisor (not in the
+ * reference; hkp_heat_loss_multi itself is unchanged).  Same labels, target,
+ * absent_mode, workspace, limits and launch scheme: fixed-order partials, no atomics,
+ * the same input gives the same bits.
+ * loss_kind: HKP_LOSS_BCE, HKP_LOSS_MSE (beta is not read; with HKP_NORM_ELEMENTS the
+ *   bits of hkp_heat_loss_multi) or HKP_LOSS_QFL, the quality focal loss (Li et al.,
+ *   "Generalized Focal Loss", 2020) against the soft target: per element in fp64, with
+ *   x = (double)heat, y = (double)t, d = x - y and
+ *   bce = (y-1) * max(log1p(-x), -100) - y * max(log(x), -100)  (hkp_heat_loss's clamps),
+ *     l = |d|^beta * bce
+ *     g = (beta * |d|^(beta-1) * sgn(d) * bce + |d|^beta * d / max((1-x)*x, 1e-12f)) / divisor
+ *   — float64 autograd of binary_cross_entropy(x, y, "none") * |x - y|^beta, cast to
+ *   fp32.  d == 0 gives l = 0 and g = +0 exactly, for every beta and also at x = y = 0
+ *   or 1: the minimum is at heat == target in every pixel.  beta in [1, 8] (finite; it
+ *   is a float: what the kernel raises to is that float); 2 takes a path of its own
+ *   without pow.  Anything else is HKP_ERR_BAD_ARG and nothing is written.
+ * norm_mode: HKP_NORM_ELEMENTS: hkp_heat_loss_multi's divisors (n*k*H*W, or H*W*A under
+ *   HKP_ABSENT_IGNORE); HKP_NORM_INSTANCES: max(P, 1), P = the present slots (flag > 0)
+ *   of the whole batch, counted on the device (no host synchronisation).  Under
+ *   HKP_ABSENT_IGNORE an absent plane's dheat is +0.0f and it adds nothing, in either
+ *   norm mode. */
+#define HKP_LOSS_QFL 2
+#define HKP_NORM_ELEMENTS 0
+#define HKP_NORM_INSTANCES 1
+int hkp_heat_loss_multi_ex(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                           int32_t absent_mode, int32_t norm_mode, float beta, const float* heat, const float* pts,
+                           float sigma, double* loss, float* dheat, void* workspace, hkp_stream_t stream);
+
 /* Keypoint evaluation (not in the reference): the peaks and counts of
  * hkp_heat_peaks, peaks [n][k][p][3] (x, y, score) and counts [n][k], matched
  * plane by plane to the labels of hkp_heat_loss_multi, pts [n][k][m][3] (u, v,
