@@ -43,7 +43,13 @@ train.py's optimizer is hkp.optim.FusedAdam and clips the gradients by their glo
 norm to that value before each step, on the GPU) and EMA_DECAY (None; a float strictly
 between 0.5 and 1: FusedAdam also keeps an exponential moving average of the parameters,
 fit() runs its test loop on it and writes model_2_1_<epoch>_ema.pth next to each
-checkpoint).
+checkpoint), and, through hkp_heat_loss_planes and with point labels only: LOSS_PARAMS may
+also hold "class_weights" (K floats, a weight per keypoint class: its planes' loss and gradient
+are scaled by it, a weight of 0 takes the class out of the loss) and "topk" (an int in 1..K:
+hard keypoint mining, per image only that many classes with the largest weighted loss are
+trained), and CLASS_LOSS (False; True: fit() prints `train class loss:` and `test class
+loss:` lines with the mean loss per pixel of each class, summed on the GPU and read once per
+epoch).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -68,3 +74,4 @@ ABSENT = "zero"
 EVAL = None
 MAX_GRAD_NORM = None
 EMA_DECAY = None
+CLASS_LOSS = False

@@ -15,7 +15,7 @@ HKP_LAYOUT_NHWC = 0
 HKP_LAYOUT_NCHW = 1
 HKP_LOSS_BCE = 0
 HKP_LOSS_MSE = 1
-HKP_LOSS_QFL = 2                   # hkp_heat_loss_multi_ex only
+HKP_LOSS_QFL = 2                   # hkp_heat_loss_multi_ex and hkp_heat_loss_planes only
 HKP_ABSENT_ZERO = 0
 HKP_ABSENT_IGNORE = 1
 HKP_NORM_ELEMENTS = 0
@@ -204,6 +204,11 @@ SIGNATURES = {
     # ... with the quality focal kind and the divisor's choice (norm_mode, beta after absent_mode)
     "hkp_heat_loss_multi_ex": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _F, _P, _P,
                                               _P, _P]),
+    # ... with plane weights [n,k], the per-plane outputs and top-k (topk after beta; weights after pts;
+    # plane_loss, plane_used after dheat)
+    "hkp_heat_loss_planes_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "hkp_heat_loss_planes": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _F,
+                                            _P, _P, _P, _P, _P, _P]),
     # evaluation: peaks/counts of hkp_heat_peaks against pts (thresholds: float array on the host)
     "hkp_peaks_match": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_F), _P, _P, _P, _P, _P, _P,
                                        _P, _P, _P]),

@@ -76,8 +76,26 @@ class _HeatLossMultiFn(torch.autograd.Function):
         return dheat * g.to(dheat.dtype), None, None, None, None, None, None
 
 
+class _HeatLossPlanesFn(torch.autograd.Function):
+    """ops.heat_loss_planes; the per-plane values leave as non-differentiable outputs."""
+
+    @staticmethod
+    def forward(ctx, heat, pts, sigma, kind, absent, beta, norm, weights, topk):
+        loss, dheat, plane_loss, plane_used = ops.heat_loss_planes(
+            heat.contiguous(), pts, sigma, kind, absent, want_grad=torch.is_grad_enabled() or heat.requires_grad,
+            beta=beta, norm=norm, weights=weights, topk=topk)
+        ctx.save_for_backward(dheat)
+        ctx.mark_non_differentiable(plane_loss, plane_used)
+        return loss, plane_loss, plane_used
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gu):
+        (dheat,) = ctx.saved_tensors
+        return (dheat * g.to(dheat.dtype),) + (None,) * 8
+
+
 def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero", beta=2.0,
-                 norm="elements"):
+                 norm="elements", weights=None, topk=None, return_planes=False):
     """mean BCE (default) or MSE between fp32 heatmaps and the fp64 Gaussian target
     (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor.
     ``pts`` [N,K,M,3] (u, v, flag) in place of both: the multi-instance target
@@ -85,7 +103,23 @@ def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, ab
     ("zero": negatives; "ignore": left out of the mean).
     ``kind="qfl"`` (``uv`` or ``pts`` labels): the quality focal loss, BCE against the
     soft target scaled by |target - heat|^``beta`` per pixel; ``norm="instances"``
-    divides the sum by the number of present instances instead of taking the mean."""
+    divides the sum by the number of present instances instead of taking the mean.
+    ``weights`` float32 [N,K], ``topk`` and ``return_planes`` (``uv`` or ``pts`` labels):
+    ops.heat_loss_planes: a weight per (image, class) plane (not > 0: the plane is not
+    labelled and leaves the loss), per image only the ``topk`` planes with the largest
+    weighted loss, and with ``return_planes`` the result is (loss, plane_loss [N,K] f64,
+    plane_used [N,K] int32), the two extras detached."""
+    if weights is not None or topk is not None or return_planes:
+        if target is not None or (pts is None) == (uv is None):
+            raise ops.HkpError("heatmap_loss: weights, topk and return_planes need pts or uv labels alone; a dense "
+                               "target is not supported")
+        ops._loss_choice("heatmap_loss", kind, norm, beta)
+        ops._planes_choice("heatmap_loss", weights, topk, heat)
+        if pts is None:
+            pts, absent = ops._uv_as_pts(heat, uv), "zero"
+        loss, plane_loss, plane_used = _HeatLossPlanesFn.apply(heat, pts, sigma, kind, absent, beta, norm, weights,
+                                                               topk)
+        return (loss, plane_loss, plane_used) if return_planes else loss
     if pts is not None:
         if target is not None or uv is not None:
             raise ops.HkpError("heatmap_loss: pass pts alone, not with target or uv")

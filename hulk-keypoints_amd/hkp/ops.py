@@ -1428,11 +1428,60 @@ def _loss_choice(who, kind, norm, beta):
     return b
 
 
-def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True, *, beta=2.0, norm="elements"):
+TOPK_MAX_K = 64                       # classes per image hkp_heat_loss_planes ranks
+
+
+def _planes_choice(who, weights, topk, heat=None):
+    """weights / topk of a loss call, checked before any kernel is called: their kinds,
+    and against the shape and device of heat when it is given as [N,K,H,W]; returns topk
+    as the int the kernel gets (0: off)."""
+    if weights is not None and not isinstance(weights, torch.Tensor):
+        raise HkpError("%s: weights must be a float32 tensor [N,K], got %s" % (who, type(weights).__name__))
+    if topk is None:
+        topk = 0
+    elif isinstance(topk, bool) or not isinstance(topk, int):
+        raise HkpError("%s: topk must be an int in 1..K or None, got %r" % (who, topk))
+    elif topk < 1:
+        raise HkpError("%s: topk %d outside 1..K" % (who, topk))
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        return topk
+    n, k = heat.shape[:2]
+    if topk and (topk > k or k > TOPK_MAX_K):
+        raise HkpError("%s: topk %d outside 1..K (K = %d, at most %d with topk)" % (who, topk, k, TOPK_MAX_K))
+    if weights is not None:
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (n, k) or weights.device != heat.device \
+                or not weights.is_contiguous():
+            raise HkpError("%s: weights must be contiguous float32 [%d,%d] on %s, got %s %s on %s"
+                           % (who, n, k, heat.device, weights.dtype, tuple(weights.shape), weights.device))
+    return topk
+
+
+def _uv_as_pts(heat, uv):
+    """uv [N,K,2] as pts [N,K,1,3]: each label one present instance."""
+    _need(heat, torch.float32, "heat_loss.heat", 4)
+    _need(uv, torch.float32, "heat_loss.uv", 3)
+    n, k = heat.shape[:2]
+    if tuple(uv.shape) != (n, k, 2):
+        raise HkpError("heat_loss: uv must be [N,K,2]")
+    return torch.cat([uv, torch.ones_like(uv[..., :1])], -1).reshape(n, k, 1, 3)
+
+
+def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True, *, beta=2.0, norm="elements",
+              weights=None, topk=None):
     """fp64 BCE/MSE over [N,K,H,W] heatmaps → (loss 0-dim f64 tensor, dheat f32 or None).
     kind="qfl" (the quality focal loss of heat_loss_multi, with its beta and norm):
-    from uv labels only, each taken as one present instance; a dense target raises."""
+    from uv labels only, each taken as one present instance; a dense target raises.
+    weights / topk (heat_loss_planes' plane weights and hard keypoint mining): from uv
+    labels only, likewise; the same two values are returned."""
     from ._lib import HKP_LOSS_BCE, HKP_LOSS_MSE, lib
+    if weights is not None or topk is not None:
+        _loss_choice("heat_loss", kind, norm, beta)
+        _planes_choice("heat_loss", weights, topk, heat)
+        if target is not None:
+            raise HkpError("heat_loss: weights / topk recompute the target from uv; a dense target is not supported")
+        pts = _uv_as_pts(heat, uv)
+        return heat_loss_planes(heat, pts, sigma, kind, "zero", want_grad, beta=beta, norm=norm, weights=weights,
+                                topk=topk)[:2]
     if kind == "qfl" or norm != "elements":
         _loss_choice("heat_loss", kind, norm, beta)
         if kind != "qfl":
@@ -1464,7 +1513,52 @@ def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True,
     return loss, dheat
 
 
-def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements"):
+def heat_loss_planes(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements",
+                     weights=None, topk=None):
+    """heat_loss_multi with a weight per (image, class) plane, the loss of every plane and
+    hard keypoint mining, one entry (hkp_heat_loss_planes) → (loss 0-dim f64, dheat f32 or
+    None, plane_loss f64 [N,K], plane_used int32 [N,K]); nothing is synchronised.
+    weights float32 [N,K] on heat's device: a plane's loss and gradient are scaled by its
+    weight; a weight that is not > 0 (0, negative, NaN) marks the plane as not labelled:
+    it leaves the loss and the divisor, its dheat is +0 and its heat is never read.
+    Weights scale, they never enter the divisor (torch's weight=).
+    topk = T in 1..K (K <= 64): per image only the T eligible planes with the largest
+    weight * summed loss are counted (OHKM); ties go to the lower class; the others keep
+    their plane_loss and get dheat +0.
+    plane_loss: the unweighted mean loss over a plane's pixels, -1 for a plane that is not
+    eligible (absent under "ignore", or not labelled).  plane_used: 1 for a counted plane.
+    The divisor: norm="elements": H*W times the counted planes; "instances": max(1, the
+    present slots of the counted planes).  With weights=None, topk=None the loss and dheat
+    are those of heat_loss_multi."""
+    from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
+                       HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    beta = _loss_choice("heat_loss_planes", kind, norm, beta)
+    if absent not in ABSENT_MODES:
+        raise HkpError("heat_loss_planes: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
+    topk = _planes_choice("heat_loss_planes", weights, topk, heat)
+    _need(heat, torch.float32, "heat_loss_planes.heat", 4)
+    _need_pts(pts, "heat_loss_planes.pts")
+    n, k, H, W = heat.shape
+    if tuple(pts.shape[:2]) != (n, k) or pts.device != heat.device:
+        raise HkpError("heat_loss_planes: pts %s on %s does not go with heat %s on %s"
+                       % (tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
+    if heat.numel() == 0 or not float(sigma) > 0:
+        raise HkpError("heat_loss_planes: empty heat or sigma %s" % (sigma,))
+    ws = torch.empty(lib().hkp_heat_loss_planes_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
+    loss = torch.empty((), device=heat.device, dtype=torch.float64)
+    dheat = torch.empty_like(heat) if want_grad else None
+    plane_loss = torch.empty((n, k), device=heat.device, dtype=torch.float64)
+    plane_used = torch.empty((n, k), device=heat.device, dtype=torch.int32)
+    kd = {"bce": HKP_LOSS_BCE, "mse": HKP_LOSS_MSE, "qfl": HKP_LOSS_QFL}[kind]
+    call("hkp_heat_loss_planes", n, k, pts.shape[2], H, W, kd,
+         HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE,
+         HKP_NORM_ELEMENTS if norm == "elements" else HKP_NORM_INSTANCES, beta, topk, _ptr(heat), _ptr(pts),
+         _ptr(weights), float(sigma), _ptr(loss), _ptr(dheat), _ptr(plane_loss), _ptr(plane_used), _ptr(ws), _stream())
+    return loss, dheat, plane_loss, plane_used
+
+
+def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements",
+                    weights=None, topk=None):
     """heat_loss against the multi-instance target of pts float32 [N,K,M,3] (u, v,
     flag), recomputed in registers → (loss 0-dim f64 tensor, dheat f32 or None).
     absent="zero": a plane without a present slot is trained against zeros;
@@ -1474,9 +1568,13 @@ def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=T
     [1, 8], as a float32; its minimum is at p == t in every pixel).
     norm="instances": the sum is divided by max(P, 1), P = the present slots of the
     batch (counted on the device), in place of the number of elements.
-    The defaults reach hkp_heat_loss_multi; "qfl" or another norm hkp_heat_loss_multi_ex."""
+    The defaults reach hkp_heat_loss_multi; "qfl" or another norm hkp_heat_loss_multi_ex;
+    weights or topk: the first two values of heat_loss_planes."""
     from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
                        HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    if weights is not None or topk is not None:
+        return heat_loss_planes(heat, pts, sigma, kind, absent, want_grad, beta=beta, norm=norm, weights=weights,
+                                topk=topk)[:2]
     beta = _loss_choice("heat_loss_multi", kind, norm, beta)
     if absent not in ABSENT_MODES:
         raise HkpError("heat_loss_multi: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))

@@ -138,6 +138,17 @@ class Trainer:
         parallelism norm="instances" divides by each rank's own count of present instances,
         as "ignore" does with its active planes: the all-reduced gradient is the mean of the
         per-rank quotients, not the sum over the global batch divided by its instances.
+        loss_params may also hold "class_weights", a sequence of K floats, and "topk"
+        (ops.heat_loss_planes; point labels only): the loss kernel then gets the plane weights
+        class_weights[None, :] * weights, weights [B,K] being forward_backward's per-image
+        weights (all one when not given; a weight that is not > 0 marks a plane as not
+        labelled), and per image only the topk planes with the largest weighted loss are
+        counted.  The class weights are put on the device once.  With either key, or with
+        weights passed to a step, trainer.plane_loss and trainer.plane_used are that step's
+        device tensors [B,K] (None otherwise); no host synchronisation is added.  Under data
+        parallelism each rank divides by its own divisor (its counted planes or their
+        instances), as for "ignore" and "instances" above; the selection is per image, so it
+        does not depend on how the batch is sharded.
         max_grad_norm / ema_decay: FusedAdam's options (hkp.optim): clip the gradients
         by their global L2 norm; keep an exponential moving average of the parameters
         (ema_weights() runs a block on it).  Under data parallelism the norm is taken in
@@ -173,8 +184,18 @@ class Trainer:
         self.params = list(model.parameters())
         self.loss_kind = loss
         self.loss_params = dict(loss_params or {})
-        if set(self.loss_params) - {"beta", "norm"}:
-            raise ValueError("loss_params may hold beta and norm, got %r" % (loss_params,))
+        if set(self.loss_params) - {"beta", "norm", "class_weights", "topk"}:
+            raise ValueError("loss_params may hold beta, norm, class_weights and topk, got %r" % (loss_params,))
+        self.topk = self.loss_params.pop("topk", None)
+        ops._planes_choice("Trainer", None, self.topk)
+        cw = self.loss_params.pop("class_weights", None)
+        if cw is not None:
+            cw = [float(v) for v in cw]
+            if len(cw) != model.num_keypoints:
+                raise ValueError("class_weights must hold %d floats, got %d" % (model.num_keypoints, len(cw)))
+        self._class_weights = cw              # the floats; the device tensor is built at the first step
+        self.class_weights = None
+        self.plane_loss = self.plane_used = None
         self.sigma = sigma
         if absent not in ops.ABSENT_MODES:
             raise ValueError("absent must be one of %s, got %r" % (", ".join(ops.ABSENT_MODES), absent))
@@ -194,18 +215,42 @@ class Trainer:
         self.bucketer = GradBucketer(self.params, bucket_mb << 20, group=group) if (use_dp or force_buckets) \
             else None
 
-    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None):
+    def _plane_weights(self, weights, device):
+        """class_weights[None, :] * weights as the kernel's [B,K] (either may be missing)."""
+        if self._class_weights is not None and (self.class_weights is None or self.class_weights.device != device):
+            self.class_weights = torch.tensor(self._class_weights, dtype=torch.float32, device=device)
+        if weights is None:
+            return None if self.class_weights is None else self.class_weights[None, :]
+        return weights if self.class_weights is None else self.class_weights[None, :] * weights
+
+    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None):
         """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
         flag: the multi-instance target, absent planes per Trainer(absent=...)).
+        weights: float32 [B,K] per-image plane weights (point labels only; see __init__).
         global_batch (SyncBN): the job's batch size — the same on every rank, x
         being this rank's hkp.parallel.shard_range share of it; lets the empty-shard
         guard run without a host collective (parallel.ShardCheck)."""
         if self.sync_bn:
             self.shard_check(x.shape[0], global_batch)
         m = self.model
+        planes = weights is not None or self._class_weights is not None or self.topk is not None
+        self.plane_loss = self.plane_used = None
+        if planes:                             # checked before the forward
+            if target is not None or (pts is None) == (uv is None):
+                raise ops.HkpError("Trainer: class_weights, topk and weights need pts or uv labels alone; a dense "
+                                   "target is not supported")
+            ops._planes_choice("Trainer", weights, self.topk)
         trace = net.Trace(self.policy)
         hm, _, _ = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace)
-        if pts is not None:
+        if planes:
+            w = self._plane_weights(weights, hm.device)
+            if w is not None:
+                w = w.expand(hm.shape[0], hm.shape[1]).contiguous()
+            lab, absent = (pts, self.absent) if pts is not None else (ops._uv_as_pts(hm, uv), "zero")
+            loss, dheat, self.plane_loss, self.plane_used = ops.heat_loss_planes(
+                hm, lab, self.sigma, self.loss_kind, absent, want_grad=True, weights=w, topk=self.topk,
+                **self.loss_params)
+        elif pts is not None:
             if uv is not None or target is not None:
                 raise ops.HkpError("Trainer: pass pts alone, not with uv or target")
             loss, dheat = ops.heat_loss_multi(hm, pts, self.sigma, self.loss_kind, self.absent, want_grad=True,
@@ -222,8 +267,8 @@ class Trainer:
                 p.grad = grads[p]
         return loss
 
-    def step(self, x, uv=None, target=None, global_batch=None, pts=None):
-        loss = self.forward_backward(x, uv, target, global_batch, pts=pts)
+    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None):
+        loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights)
         self.opt.step()
         return loss
 

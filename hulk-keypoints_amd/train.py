@@ -31,6 +31,16 @@ buffers and are saved as they stand.
 With config.LOSS = "qfl" (default "bce": nothing changes) the train and the test loop take
 the quality focal loss of hkp_heat_loss_multi_ex, with config.LOSS_PARAMS's beta and norm;
 it needs point labels ((u, v) or instances), which main()'s datasets give.
+
+config.LOSS_PARAMS may also hold "class_weights" (K floats: a weight per keypoint class, put on
+the device once) and "topk" (per image only that many classes with the largest weighted loss
+are trained: hard keypoint mining), both through hkp_heat_loss_planes and point labels only.
+With config.CLASS_LOSS = True (default False: nothing changes) the loss also returns its
+value per (image, class) plane; fit() adds them up per class on the device, over the planes
+that took part in the labels (plane_loss >= 0), reads the sums once per epoch and prints
+`train class loss: c0 ... cK-1` after `train loss:` and `test class loss: ...` after
+`test loss:`: the unweighted mean loss per pixel of each class (nan for a class that no
+image labelled).  Under data parallelism rank 0 prints its own shard's train values.
 """
 import contextlib
 import os
@@ -41,9 +51,9 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from config import *  # noqa: F401,F403
-from config import (ABSENT, BACKBONE, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED, GAUSS_SIGMA,
-                    GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, LOSS_PARAMS, MAX_GRAD_NORM,
-                    NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
+from config import (ABSENT, BACKBONE, CLASS_LOSS, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED,
+                    GAUSS_SIGMA, GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, LOSS_PARAMS,
+                    MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
@@ -54,6 +64,8 @@ use_cuda = True
 optimizer = None
 keypoints = None
 _bucketer = None
+_class_weights = {}     # device -> LOSS_PARAMS["class_weights"] as a float32 tensor, built once
+_class_acc = None       # CLASS_LOSS: float64 [2,K] on the device, per class the sum of plane_loss and the planes
 
 
 def _rank0():
@@ -66,15 +78,56 @@ def forward(sample_batched, model):
     return _loss(model.forward(img), gt)
 
 
+def _planes_kw(pred_gauss):
+    """LOSS_PARAMS' class_weights as heatmap_loss's weights [B,K] (the other keys pass as they
+    are), and return_planes with CLASS_LOSS; the parameters unchanged when neither is set."""
+    if "class_weights" not in LOSS_PARAMS and not CLASS_LOSS:
+        return LOSS_PARAMS
+    kw = {k: v for k, v in LOSS_PARAMS.items() if k != "class_weights"}
+    if "class_weights" in LOSS_PARAMS:
+        dev = pred_gauss.device
+        key = (dev, tuple(float(v) for v in LOSS_PARAMS["class_weights"]))
+        if key not in _class_weights:
+            _class_weights[key] = torch.tensor(key[1], dtype=torch.float32, device=dev)
+        if _class_weights[key].numel() != pred_gauss.shape[1]:
+            raise ops.HkpError("LOSS_PARAMS['class_weights'] must hold %d floats" % pred_gauss.shape[1])
+        kw["weights"] = _class_weights[key][None, :].expand(pred_gauss.shape[0], -1).contiguous()
+    if CLASS_LOSS:
+        kw["return_planes"] = True
+    return kw
+
+
+def _class_loss_add(out):
+    """heatmap_loss(return_planes=True)'s result: the per-class sums go into _class_acc on
+    the device (no synchronisation); returns the loss."""
+    global _class_acc
+    loss, plane_loss, _ = out
+    on = plane_loss >= 0
+    add = torch.stack([torch.where(on, plane_loss, torch.zeros_like(plane_loss)).sum(0), on.sum(0).double()])
+    _class_acc = add if _class_acc is None else _class_acc + add
+    return loss
+
+
+def _class_loss_line(what):
+    """Prints `<what> class loss: c0 ... cK-1` from _class_acc (its one read) and clears it."""
+    global _class_acc
+    if _class_acc is not None and _rank0():
+        sums, cnt = _class_acc.tolist()
+        print(what + " class loss:", *[s / c if c else float("nan") for s, c in zip(sums, cnt)])
+    _class_acc = None
+
+
 def _loss(pred_gauss, gt):
+    kw = _planes_kw(pred_gauss)
+    done = _class_loss_add if CLASS_LOSS else (lambda out: out)
     if gt.dim() == 3:   # (u, v) labels → the loss kernel recomputes the Gaussian target in registers
-        return hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
-                                         **LOSS_PARAMS)
+        return done(hkp_autograd.heatmap_loss(pred_gauss, uv=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA,
+                                              kind=LOSS, **kw))
     if gt.dim() == 4 and gt.shape != pred_gauss.shape and gt.shape[-1] == 3 and gt.is_floating_point():
         # instance labels [B,K,M,3] (u, v, flag): the multi-instance target, absent planes per ABSENT
-        return hkp_autograd.heatmap_loss(pred_gauss, pts=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA, kind=LOSS,
-                                         absent=ABSENT, **LOSS_PARAMS)
-    return hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS, **LOSS_PARAMS)
+        return done(hkp_autograd.heatmap_loss(pred_gauss, pts=gt.cuda().float().contiguous(), sigma=GAUSS_SIGMA,
+                                              kind=LOSS, absent=ABSENT, **kw))
+    return done(hkp_autograd.heatmap_loss(pred_gauss, target=gt.cuda().double().contiguous(), kind=LOSS, **kw))
 
 
 def eval_forward(sample_batched, model, metrics, peak_kw):
@@ -132,7 +185,9 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
     if EVAL is not None:            # every rank walks the whole test set: no reduction needed
         from hkp.metrics import from_config
         metrics, peak_kw = from_config(EVAL, model.num_keypoints)
+    global _class_acc
     for epoch in range(epochs):
+        _class_acc = None
         if hasattr(getattr(train_data, "sampler", None), "set_epoch"):
             train_data.sampler.set_epoch(epoch)
         if hasattr(getattr(train_data, "dataset", None), "set_epoch"):
@@ -151,6 +206,7 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
                 print("\r", end="")
         if _rank0():
             print("train loss:", train_loss / max(i_batch, 1))   # reference divides by i_batch (train.py:40)
+        _class_loss_line("train")
         test_loss = 0.0
         i_batch = 0
         if metrics is not None:
@@ -165,6 +221,8 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
                 test_loss += loss.item()
             if _rank0():
                 print("test loss:", test_loss / max(i_batch, 1))
+            _class_loss_line("test")
+            if _rank0():
                 if metrics is not None:
                     print("test eval:", metrics.summary())
                 if has_ema and epoch % 2 == 0:

@@ -766,6 +766,49 @@ int hkp_heat_loss_multi_ex(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W
                            int32_t absent_mode, int32_t norm_mode, float beta, const float* heat, const float* pts,
                            float sigma, double* loss, float* dheat, void* workspace, hkp_stream_t stream);
 
+/* hkp_heat_loss_multi_ex with a weight per (image, class) plane, the per-plane loss
+ * values and online hard keypoint mining (OHKM: Chen et al., "Cascaded Pyramid
+ * Network", 2018); not in the reference, and the entries above are unchanged.  Same
+ * labels, target, loss kinds (beta as there), absent_mode, per-element formulas, clamps
+ * and fp64 arithmetic, the 16-byte and the scalar path, fixed-order sums, no atomics:
+ * the same input gives the same bits.  Every decision is taken on the device, with no
+ * host synchronisation.
+ * eligible:  a plane (b, c) is eligible unless it has no present slot under
+ *            HKP_ABSENT_IGNORE, or weights is given and !(weights[b][c] > 0): zero,
+ *            negative and NaN all mean "not labelled" (the instance flag's rule).  The
+ *            heat of a plane that is not eligible is never read into the result; its
+ *            dheat is +0.0f, its plane_loss -1.0 (every kind is >= 0) and plane_used 0.
+ * S[b][c]:   the fp64 sum of the unweighted per-element losses of an eligible plane: its
+ *            block partials added in chunk order.  plane_loss[b][c] = S / (H*W); two
+ *            planes with the same heat and labels get the same bits.
+ * topk = T:  0: every eligible plane is counted.  1 <= T <= k <= 64: per image the
+ *            eligible planes are ranked by r = (double)w * S (w = 1 without weights) and
+ *            the T largest are counted; equal r goes to the lower class, a NaN r ranks
+ *            above everything, fewer than T eligible planes are all counted.
+ *            plane_used is 1 for a counted plane; an eligible plane that is not counted
+ *            keeps its plane_loss and gets dheat +0.0f.
+ * divisor D: HKP_NORM_ELEMENTS: H*W*C, C = the counted planes of the batch (C = 0: loss 0,
+ *            dheat 0); HKP_NORM_INSTANCES: max(P, 1), P = the present slots of the
+ *            counted planes.  Weights never enter the divisor.
+ * values:    loss = (sum over the counted planes, in plane order, of (double)w * S) / D;
+ *            dheat = (float)(g * (double)w), g the fp64 value hkp_heat_loss_multi_ex
+ *            forms for that element with divisor D.  With w == 1 (or no weights) the
+ *            product is exact: the bits of hkp_heat_loss_multi_ex.
+ * launches:  topk == 0: one pass over the planes between a small pre- and post-kernel.
+ *            topk > 0: a first pass that reads the heat and writes only the partials, a
+ *            one-block kernel that ranks and counts, and a second pass that writes dheat
+ *            and reads the heat of the counted planes only.  The loss comes from the
+ *            stored S either way, so topk == k gives the bits of topk == 0.
+ * weights [n][k] fp32, plane_loss [n][k] fp64 and plane_used [n][k] int32 are nullable,
+ * as is dheat.  Limits as hkp_heat_loss_multi_ex, and 0 <= topk <= k, k <= 64 when
+ * topk > 0; anything else is HKP_ERR_BAD_ARG and nothing is launched or written.
+ * workspace: hkp_heat_loss_planes_workspace(n, k, H, W) bytes. */
+int64_t hkp_heat_loss_planes_workspace(int32_t n, int32_t k, int32_t H, int32_t W);
+int hkp_heat_loss_planes(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                         int32_t absent_mode, int32_t norm_mode, float beta, int32_t topk, const float* heat,
+                         const float* pts, const float* weights, float sigma, double* loss, float* dheat,
+                         double* plane_loss, int32_t* plane_used, void* workspace, hkp_stream_t stream);
+
 /* Keypoint evaluation (not in the reference): the peaks and counts of
  * hkp_heat_peaks, peaks [n][k][p][3] (x, y, score) and counts [n][k], matched
  * plane by plane to the labels of hkp_heat_loss_multi, pts [n][k][m][3] (u, v,
