@@ -49,7 +49,13 @@ are scaled by it, a weight of 0 takes the class out of the loss) and "topk" (an 
 hard keypoint mining, per image only that many classes with the largest weighted loss are
 trained), and CLASS_LOSS (False; True: fit() prints `train class loss:` and `test class
 loss:` lines with the mean loss per pixel of each class, summed on the GPU and read once per
-epoch).
+epoch), and SYNTH (None: train.py reads data/<dataset>/ as the reference does; a dict such as
+{"train": 512, "test": 128, "seed": 0, "classes": ("cap", "tail", "crossing", "blob"),
+"instances": 8} — "train" and "test" are scenes per epoch, every other key a keyword argument of
+hkp.synth.CableScenes —: train.py's main() needs no data/ directory, both sets are procedural
+cable scenes rendered on the GPU, hkp_synth_cables_u8, with instance labels [K,M,3] of M =
+"instances" slots; the train set draws new scenes every epoch, the test set is fixed and
+comes from seed + 1; NUM_KEYPOINTS must equal the number of classes).
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -75,3 +81,4 @@ EVAL = None
 MAX_GRAD_NORM = None
 EMA_DECAY = None
 CLASS_LOSS = False
+SYNTH = None

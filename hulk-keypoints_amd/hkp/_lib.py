@@ -106,6 +106,29 @@ class ResampleImage(ctypes.Structure):
 
 assert ctypes.sizeof(ResampleImage) == 64
 
+# the cable-scene renderer's ABI (include/hulkkp.h)
+HKP_SYNTH_MAX_DIM = 4096
+HKP_SYNTH_MAX_SEGS = 512
+
+
+class SynthSeg(ctypes.Structure):
+    """hkp_synth_seg (hkp_synth_cables_u8): one capsule in the kernel's fixed point."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("ux", ctypes.c_int32), ("uy", ctypes.c_int32),
+                ("len", ctypes.c_int32), ("r", ctypes.c_int32), ("r_in2", ctypes.c_int32), ("r_out2", ctypes.c_int32),
+                ("r2", ctypes.c_int32), ("inv", ctypes.c_uint32), ("inv_r2", ctypes.c_uint32),
+                ("bgr", ctypes.c_uint8 * 4), ("shade", ctypes.c_int32), ("arc", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+class SynthScene(ctypes.Structure):
+    """hkp_synth_scene (hkp_synth_cables_u8): one image's pieces and background."""
+    _fields_ = [("seg_off", ctypes.c_int32), ("seg_cnt", ctypes.c_int32), ("key", ctypes.c_uint32 * 2),
+                ("bg0", ctypes.c_uint8 * 4), ("bg1", ctypes.c_uint8 * 4), ("cell_log2", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 9)]
+
+
+assert ctypes.sizeof(SynthSeg) == 64 and ctypes.sizeof(SynthScene) == 64
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -227,6 +250,9 @@ SIGNATURES = {
     # antialiased resize (records_host / tables_host: host copies, validated; records / tables: device copies)
     "hkp_resample_u8": (ctypes.c_int, [_I32, _P, _I64, ctypes.POINTER(ResampleImage), _P, _P, _P, _I64, _I32, _I32,
                                        _P, _P]),
+    # procedural cable scenes (scenes_host / segs_host: host copies, validated; scenes / segs: device copies)
+    "hkp_synth_cables_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, ctypes.POINTER(SynthScene), _P,
+                                           ctypes.POINTER(SynthSeg), _P, _I32, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

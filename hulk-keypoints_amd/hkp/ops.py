@@ -574,6 +574,28 @@ def warp_affine_u8(img, plan, out_hw=None):
     return out
 
 
+def synth_cables_u8(plan, out=None):
+    """Procedural cable scenes (csrc/synth.hip): the batch's hkp.synth.SynthPlan (one scene
+    per image) → uint8 [B,H,W,3] BGR on the current device, one launch on the current
+    stream; the plan's records are uploaded on that stream.  out: a uint8 [B,H,W,3] device
+    tensor to render into (rows may start at any byte address), else a new one."""
+    from ._lib import HKP_SYNTH_MAX_DIM
+    n, (h, w) = getattr(plan, "n", None), getattr(plan, "hw", (0, 0))
+    if not n or not (1 <= h <= HKP_SYNTH_MAX_DIM and 1 <= w <= HKP_SYNTH_MAX_DIM):
+        raise HkpError("synth_cables_u8: need a SynthPlan of B >= 1 images of H, W in 1..%d, got %r %r"
+                       % (HKP_SYNTH_MAX_DIM, n, (h, w)))
+    if out is None:
+        out = torch.empty((n, h, w, 3), device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "synth_cables_u8.out", 4)
+        if tuple(out.shape) != (n, h, w, 3):
+            raise HkpError("synth_cables_u8: out must be %s, got %s" % ((n, h, w, 3), tuple(out.shape)))
+    scenes, segs = plan.device_arrays(out.device)
+    call("hkp_synth_cables_u8", n, h, w, _ptr(out), plan.scenes, _ptr(scenes), plan.segs, _ptr(segs), plan.nsegs,
+         _stream())
+    return out
+
+
 def resize_u8(img, h, w, interp="bilinear"):
     """img uint8 [B,Hs,Ws,3] → [B,h,w,3]: the affine warp with the half-pixel-centre
     resize matrix and replicated borders.  No antialiasing: large reductions alias."""

@@ -15,6 +15,10 @@
                     one batch ahead on a side stream) and fed to the model as
                     [B,H,W,3] uint8, where the stem's operand pack applies ToTensor;
                     labels travel as (u, v) and the loss kernel makes the target.
+  SynthDataset      not in the reference: procedural cable scenes (hkp.synth.CableScenes)
+                    rendered on the GPU, hkp_synth_cables_u8, with instance labels from the
+                    scene description; DeviceBatches takes a branch of its own for it (no
+                    workers, no host image, no copy).
 """
 import os
 
@@ -225,6 +229,62 @@ class KeypointsDataset(Dataset):
         return len(self.labels)
 
 
+class SynthDataset(Dataset):
+    """`length` procedural cable scenes of `scenes` (a hkp.synth.CableScenes) at hw = (h, w),
+    rendered on the GPU; the labels are instance labels pts [K,M,3] (u, v, flag) with
+    K = len(scenes.classes) and M = scenes.instances.  Item i of this rank is scene
+    rank + i * world of the epoch set_epoch() gave (train.py's fit() calls it: new scenes
+    every epoch); fixed=True ignores the epoch (a test set).  __getitem__ is the DataLoader
+    idiom of train.py (keep num_workers=0): one image rendered by a B = 1 launch, through
+    `transform`; items are (img, pts) with return_uv=True, else (img, gaussians) from
+    hkp_gauss_target_multi.  raw(i) returns (uint8 [H,W,3] BGR on the host, fp32 [K,M,3]
+    on the device)."""
+
+    def __init__(self, scenes, length, hw, epoch=0, fixed=False, rank=0, world=1, transform=transform, return_uv=True,
+                 device="cuda", gauss_sigma=8):
+        if int(length) < 1 or int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("SynthDataset: need length >= 1 and 0 <= rank < world, got %r, %r, %r"
+                             % (length, rank, world))
+        self.scenes, self.length = scenes, int(length)
+        self.img_height, self.img_width = int(hw[0]), int(hw[1])
+        self.num_keypoints, self.instances = len(scenes.classes), scenes.instances
+        self.epoch, self.fixed, self.rank, self.world = int(epoch), bool(fixed), int(rank), int(world)
+        self.transform, self.return_uv, self.device, self.gauss_sigma = transform, return_uv, device, gauss_sigma
+
+    def __len__(self):
+        return (self.length - self.rank + self.world - 1) // self.world
+
+    def set_epoch(self, epoch):
+        """The epoch the scenes are drawn under (ignored with fixed=True)."""
+        if not self.fixed:
+            self.epoch = int(epoch)
+
+    def scene_index(self, i):
+        if not 0 <= int(i) < len(self):
+            raise IndexError(i)
+        return self.rank + int(i) * self.world
+
+    def plan(self, items, epoch=None):
+        """The SynthPlan of dataset items `items` under `epoch` (None, or fixed=True: the
+        dataset's own)."""
+        e = self.epoch if epoch is None or self.fixed else int(epoch)
+        return self.scenes.plan([self.scene_index(i) for i in items], e, (self.img_height, self.img_width))
+
+    def raw(self, index):
+        plan = self.plan([index])
+        with torch.cuda.device(self.device):
+            img = ops.synth_cables_u8(plan)[0].cpu().numpy()
+        return img, torch.from_numpy(plan.pts[0]).to(self.device)
+
+    def __getitem__(self, index):
+        img, pts = self.raw(index)
+        img = self.transform(img)
+        if self.return_uv:
+            return img, pts
+        return img, ops.gauss_target_multi(pts.unsqueeze(0).contiguous(), self.img_height, self.img_width,
+                                           self.gauss_sigma)[0]
+
+
 class _RawView(Dataset):
     """(uint8 [H,W,3] BGR, float32 [K,2]) host items of a KeypointsDataset — what
     DeviceBatches' decode workers produce."""
@@ -376,12 +436,22 @@ class DeviceBatches:
     the labels that go on are plan.apply_uv(uv).  Build the dataset with the same
     `resize`, so that its stored labels are in each file's own pixel coordinates.
     With decode="device" a batch of one JPEG geometry is reconstructed on the device
-    and then resampled; a batch of mixed geometry takes the host decode."""
+    and then resampled; a batch of mixed geometry takes the host decode.
+
+    A SynthDataset takes a branch of its own: no workers, no host image, no copy.  Each
+    batch is rendered on the copy stream by one hkp_synth_cables_u8 launch from the plan of
+    (scenes, this epoch — the dataset's own with fixed=True —, its scene indices) and its
+    pts uploaded from the plan;
+    `geometric` and `augment` then apply exactly as for decoded batches, under the scene
+    indices.  `resize` and decode="device" raise for it."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, drop_last=False, device="cuda", workers=0,
                  prefetch=4, decode="host", augment=None, geometric=None, resize=None):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
+        if isinstance(dataset, SynthDataset) and (resize is not None or decode != "host"):
+            raise ValueError("DeviceBatches: a SynthDataset is rendered on the device at its own size: resize= and "
+                             "decode='device' do not apply to it")
         self.ds, self.bs, self.shuffle, self.seed, self.drop_last = dataset, batch_size, shuffle, seed, drop_last
         self.device = torch.device(device)
         self.workers, self.prefetch, self.decode = workers, prefetch, decode
@@ -440,6 +510,9 @@ class DeviceBatches:
         if self.drop_last and batches and len(batches[-1]) < self.bs:
             batches.pop()
         copy_stream = torch.cuda.Stream(self.device)
+        if isinstance(self.ds, SynthDataset):
+            yield from self._synth_batches(batches, epoch, copy_stream)
+            return
         host = self._host_batches(batches)
         staged = iter(batches)                 # host batches come in this order
 
@@ -491,3 +564,40 @@ class DeviceBatches:
             img.record_stream(cur)
             uv.record_stream(cur)
             yield img, uv
+
+    def _synth_batches(self, batches, epoch, copy_stream):
+        """__iter__ for a SynthDataset: render, warp and augment on the copy stream, one
+        batch ahead of the consumer."""
+        ds = self.ds
+
+        def stage(items):
+            idx = [ds.scene_index(i) for i in items]
+            with torch.cuda.device(self.device), torch.cuda.stream(copy_stream):
+                plan = ds.plan(items, epoch)
+                img = ops.synth_cables_u8(plan)
+                pts = torch.from_numpy(plan.pts)
+                buf = plan                     # the plan's pinned records live as long as the batch
+                if self.geometric is not None:
+                    gplan = self.geometric.plan(idx, epoch, uvs=pts, hw=(img.shape[1], img.shape[2]))
+                    img = ops.warp_affine_u8(img, gplan)
+                    pts = gplan.apply_points(pts)
+                    buf = (buf, gplan)
+                if self.augment is not None:
+                    aplan = self.augment.plan(idx, epoch)
+                    img = ops.augment_u8(img, aplan)
+                    buf = (buf, aplan)
+                pts = pts.pin_memory()
+                ptsd = pts.to(self.device, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(copy_stream)
+            return img, ptsd, ev, (buf, pts)
+
+        nxt = stage(batches[0]) if batches else None
+        for bi in range(len(batches)):
+            img, pts, ev, buf = nxt
+            nxt = stage(batches[bi + 1]) if bi + 1 < len(batches) else None
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(ev)
+            img.record_stream(cur)
+            pts.record_stream(cur)
+            yield img, pts

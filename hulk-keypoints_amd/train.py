@@ -28,6 +28,13 @@ model_2_1_<epoch>.pth (the raw weights, needed to resume) fit() writes
 model_2_1_<epoch>_ema.pth.  The EMA covers the parameters; BN running statistics are
 buffers and are saved as they stand.
 
+With config.SYNTH set (default None: nothing changes) main() needs no data/ directory: both
+sets are procedural cable scenes rendered on the GPU (hkp.synth.CableScenes through
+src.dataset.SynthDataset) with instance labels [K,M,3]; the train set draws new scenes every
+epoch, the test set is fixed and comes from seed + 1.  NUM_KEYPOINTS must equal the number
+of classes; GEOMETRIC_AUGMENTATION and RESIZE do not go with it here (DeviceBatches takes
+geometric= for a SynthDataset).
+
 With config.LOSS = "qfl" (default "bce": nothing changes) the train and the test loop take
 the quality focal loss of hkp_heat_loss_multi_ex, with config.LOSS_PARAMS's beta and norm;
 it needs point labels ((u, v) or instances), which main()'s datasets give.
@@ -53,11 +60,11 @@ from torch.utils.data import DataLoader
 from config import *  # noqa: F401,F403
 from config import (ABSENT, BACKBONE, CLASS_LOSS, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED,
                     GAUSS_SIGMA, GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, LOSS_PARAMS,
-                    MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, batch_size, epochs)
+                    MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, SYNTH, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
-from src.dataset import KeypointsDataset, domain_randomization, transform
+from src.dataset import KeypointsDataset, SynthDataset, domain_randomization, transform
 from src.model import KeypointsGauss
 
 use_cuda = True
@@ -255,12 +262,22 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
     if RESIZE is not None:                          # image files of any size; train and test set alike
         from hkp.resample import Resize
         resize = Resize(filter=RESIZE, **RESIZE_PARAMS)
-    train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir, "data/%s/train/keypoints" % dataset_dir,
-                                     NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA,
-                                     return_uv=True, geometric=geometric, resize=resize, instances=INSTANCES)
-    test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
-                                    NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
-                                    return_uv=True, resize=resize, instances=INSTANCES)
+    if SYNTH is not None:                           # procedural scenes: no data/ directory
+        from hkp.synth import from_config as synth_from_config
+        if geometric is not None or resize is not None:
+            raise ValueError("config.SYNTH does not go with GEOMETRIC_AUGMENTATION or RESIZE in train.py")
+        train_scenes, test_scenes, n_train, n_test = synth_from_config(SYNTH, NUM_KEYPOINTS)
+        train_dataset = SynthDataset(train_scenes, n_train, (IMG_HEIGHT, IMG_WIDTH), transform=train_transform,
+                                     gauss_sigma=GAUSS_SIGMA)
+        test_dataset = SynthDataset(test_scenes, n_test, (IMG_HEIGHT, IMG_WIDTH), fixed=True, gauss_sigma=GAUSS_SIGMA)
+    else:
+        train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir,
+                                         "data/%s/train/keypoints" % dataset_dir, NUM_KEYPOINTS, IMG_HEIGHT,
+                                         IMG_WIDTH, train_transform, gauss_sigma=GAUSS_SIGMA, return_uv=True,
+                                         geometric=geometric, resize=resize, instances=INSTANCES)
+        test_dataset = KeypointsDataset("data/%s/test/images" % dataset_dir, "data/%s/test/keypoints" % dataset_dir,
+                                        NUM_KEYPOINTS, IMG_HEIGHT, IMG_WIDTH, transform, gauss_sigma=GAUSS_SIGMA,
+                                        return_uv=True, resize=resize, instances=INSTANCES)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset) if world > 1 else None
     train_data = DataLoader(train_dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
                             num_workers=workers)

@@ -1042,6 +1042,94 @@ int hkp_resample_u8(int32_t n, const uint8_t* img_in, int64_t in_bytes, const hk
                     const hkp_resample_image* records, const int32_t* tables_host, const int32_t* tables,
                     int64_t table_words, int32_t h, int32_t w, uint8_t* img_out, hkp_stream_t stream);
 
+/* ------------------------------------------- procedural cable scenes ---- */
+/* Renders uint8 [n][h][w][3] BGR pictures of cables from a scene description
+ * (hkp/synth.py samples it and makes the labels): a value-noise background, then
+ * the scene's pieces composited in index order.  Every piece is a capsule (a disc
+ * is a capsule of length 0).  Integer pixel coordinates are pixel centres.  The
+ * arithmetic is integer only and part of the contract (tests/_synth_ref.py restates
+ * it in numpy); >> is an arithmetic shift (floor).
+ *
+ * Background of pixel (x, y), scene key (k0, k1), cell_log2 = L; octave o = 0, 1
+ * has shift sh = L - o:
+ *   ix = x >> sh,  fx = ((x & ((1 << sh) - 1)) << 8) >> sh      (Q8; the same for y)
+ *   v(i, j) = low 8 bits of the first word of Philox4x32-10(counter (i, j, o, 0), key)
+ *   top = v(ix, iy)*(256 - fx) + v(ix+1, iy)*fx,  bot = v(ix, iy+1)*(256 - fx) + v(ix+1, iy+1)*fx
+ *   n_o = (top*(256 - fy) + bot*fy + 32768) >> 16
+ *   n = (3*n_0 + n_1 + 2) >> 2,   bg_c = bg0_c + (((bg1_c - bg0_c)*n + 128) >> 8)
+ *
+ * Piece, with P = (16 x, 16 y) the pixel in Q4:
+ *   a  = P - (x0, y0)
+ *   s  = clamp((ax*ux + ay*uy) >> 14, 0, len)                    Q4 along the axis
+ *   c  = a - ((s*ux) >> 14, (s*uy) >> 14)
+ *   d2 = cx*cx + cy*cy                                            Q8
+ *   alpha = 256 if d2 <= r_in2;  0 if d2 >= r_out2;  else ((r_out2 - d2)*inv) >> 24
+ *   lum   = 256 - ((shade * ((min(d2, r2)*inv_r2) >> 24)) >> 8)
+ *   colour_c = (bgr_c*lum + 128) >> 8
+ * with r the radius in Q4, r_in2 = (r - 8)^2, r_out2 = (r + 8)^2 (half a pixel either
+ * side), r2 = r*r, inv = floor(2^32 / (r_out2 - r_in2)), inv_r2 = floor(2^32 / r2).
+ *
+ * Word widths, at the validated limits (|x0|, |y0| <= 2^17, P < 2^16, |ux|, |uy| <= 2^14,
+ * len <= 2^18, 16 <= r <= 512):
+ *   a.u        |a| < 2^18 per axis, so |ax*ux + ay*uy| < 2*2^18*2^14 = 2^33: 64 bits.
+ *   s*u        s <= 2^18, |u| <= 2^14: up to 2^32: 64 bits.
+ *   c.c        |c| <= |a| + 2^18 < 2^19 per axis, d2 < 2^39: 64 bits.  Only d2 < r_out2
+ *              <= 520^2 < 2^19 is used after the comparison, so all that follows is narrow.
+ *   (r_out2 - d2)*inv   in the ramp r_in2 < d2, so the factor is at most D - 1 with
+ *              D = r_out2 - r_in2 = 32 r <= 2^14, and (D - 1)*floor(2^32 / D) < 2^32: 32 bits
+ *              unsigned, and alpha <= 255 there.
+ *   min(d2, r2)*inv_r2  reaches r2*floor(2^32 / r2), which is 2^32 exactly when r2 is a
+ *              power of two (r = 16, 32, ... 512): 64 bits (33 would do).  The quotient is <= 256.
+ *   everything else (the bilinear noise < 2^24, the blends < 2^17) fits 32 bits.
+ *
+ * Compositing: the pieces with alpha > 0 at the pixel are walked in ascending index.
+ * A piece continues the current run when its arc id equals the run's and its index is
+ * the run's last index + 1; otherwise the run ends and a new one starts.  A run keeps
+ * the piece with the largest alpha, then the smallest d2, then the later index; when
+ * it ends it is blended over what lies below:
+ *   out_c = (run_c*alpha + out_c*(256 - alpha) + 128) >> 8
+ * so a joint is not blended twice and a later strand's rim lies over an earlier one. */
+#define HKP_SYNTH_MAX_DIM 4096
+#define HKP_SYNTH_MAX_SEGS 512     /* pieces per image */
+#define HKP_SYNTH_TILE_H 16        /* one block's tile of one image (pixels) */
+#define HKP_SYNTH_TILE_W 64
+
+typedef struct hkp_synth_seg {    /* 64 bytes */
+    int32_t x0, y0;        /* start vertex, Q4, |.| <= 2^17                      */
+    int32_t ux, uy;        /* unit direction, Q14, |.| <= 2^14                   */
+    int32_t len;           /* length, Q4, 0 .. 2^18                              */
+    int32_t r;             /* radius, Q4, 16 .. 512 (1 .. 32 px)                 */
+    int32_t r_in2, r_out2; /* (r - 8)^2, (r + 8)^2                               */
+    int32_t r2;            /* r*r                                                */
+    uint32_t inv, inv_r2;  /* floor(2^32 / (r_out2 - r_in2)), floor(2^32 / r2)   */
+    uint8_t bgr[4];        /* B, G, R, unused                                    */
+    int32_t shade;         /* 0 .. 256: how much darker the rim is               */
+    int32_t arc;           /* run id: consecutive pieces of one arc form a run   */
+    int32_t reserved[2];   /* 0 */
+} hkp_synth_seg;
+
+typedef struct hkp_synth_scene {  /* 64 bytes */
+    int32_t seg_off;       /* first piece of the image in the table              */
+    int32_t seg_cnt;       /* 0 .. HKP_SYNTH_MAX_SEGS                            */
+    uint32_t key[2];       /* Philox key of the background                       */
+    uint8_t bg0[4], bg1[4];/* the two background colours: B, G, R, unused        */
+    int32_t cell_log2;     /* 4 .. 12: octave 0's lattice cell is 1 << cell_log2 px */
+    int32_t reserved[9];   /* 0 */
+} hkp_synth_scene;
+
+/* One launch for the batch, no workspace, no input image: img_out is written whole.
+ * scenes_host / scenes hold the same n records and segs_host / segs the same nsegs
+ * pieces: the host copies are validated here before anything is launched or written
+ * (device memory is not read), the device copies are what the kernel reads.  Checked:
+ * 1 <= h, w <= HKP_SYNTH_MAX_DIM; seg_off >= 0, 0 <= seg_cnt <= HKP_SYNTH_MAX_SEGS and
+ * seg_off + seg_cnt <= nsegs; every piece of every image within the limits above with
+ * r_in2, r_out2, r2, inv and inv_r2 equal to what r gives; 4 <= cell_log2 <= 12;
+ * reserved == 0.  Rows leave as dwords when w % 4 == 0 and img_out is 4-byte aligned,
+ * as bytes otherwise. */
+int hkp_synth_cables_u8(int32_t n, int32_t h, int32_t w, uint8_t* img_out, const hkp_synth_scene* scenes_host,
+                        const hkp_synth_scene* scenes, const hkp_synth_seg* segs_host, const hkp_synth_seg* segs,
+                        int32_t nsegs, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
