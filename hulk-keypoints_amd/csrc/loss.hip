@@ -3,7 +3,7 @@
 //  * hkp_heat_loss   train.py:21,25 — nn.BCELoss()(pred.double(), gt) with the
 //                    Gaussian target (dataset.py:36-44) read from a dense fp64
 //                    tensor or recomputed in registers from (u, v); MSE (train.py:13)
-//                    selectable.  fp64 loss, fp64 per-element gradient:
+//                    selectable.  fp64 loss, fp64 per-element gradient (loss_elem.h):
 //                      BCE  l = (y-1)*max(log1p(-p),-100) - y*max(log p,-100)
 //                           g = (p-y) / max((1-p)*p, EPS) / N
 //                      MSE  l = (p-y)^2,  g = 2 (p-y) / N
@@ -18,6 +18,7 @@
 //  * hkp_head_fc_bwd fc 1x1 (resnet_dilated.py:16) grads: dfeat (NHWC), dW, db for
 //                    the K used rows; rows >= K get exactly zero.
 #include "common.h"
+#include "loss_elem.h"
 
 #pragma clang fp contract(off)
 
@@ -49,17 +50,6 @@ __device__ __forceinline__ LerpB lerp_b(int o, int in, int out, float scale) {
     return r;
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    return t;
-}
-
 template <int KIND, bool DENSE>
 __global__ __launch_bounds__(256) void heat_loss_kernel(long total, int H, int W, float den, double inv_n,
                                                        const float* __restrict__ p, const double* __restrict__ gt,
@@ -81,15 +71,8 @@ __global__ __launch_bounds__(256) void heat_loss_kernel(long total, int H, int W
             y = (double)expf(-(dx * dx + dy * dy) / den);
         }
         const double x = (double)p[i];
-        double l, g;
-        if constexpr (KIND == HKP_LOSS_BCE) {
-            l = (y - 1.0) * fmax(log1p(-x), -100.0) - y * fmax(log(x), -100.0);
-            g = (x - y) / fmax((1.0 - x) * x, (double)1e-12f) * inv_n;
-        } else {
-            l = (x - y) * (x - y);
-            g = 2.0 * inv_n * (x - y);
-        }
-        acc += l;
+        double g;
+        acc += loss_elem<KIND>(x, y, inv_n, 0.0, 0.0, &g);   // BCE or MSE: no beta
         if (dheat) dheat[i] = (float)g;
     }
     const double t = block_sum_d(acc, red);

@@ -1478,6 +1478,23 @@ def _planes_choice(who, weights, topk, heat=None):
     return topk
 
 
+def _multi_loss_args(who, heat, pts, sigma, absent, planes=None):
+    """The checks heat_loss_multi and heat_loss_planes share, after _loss_choice and in this
+    order: the absent mode; with planes = (weights, topk), _planes_choice; heat, pts and
+    that they go together; sigma.  Returns topk as _planes_choice does (0 without planes)."""
+    if absent not in ABSENT_MODES:
+        raise HkpError("%s: unknown absent %r (known: %s)" % (who, absent, ", ".join(ABSENT_MODES)))
+    topk = _planes_choice(who, planes[0], planes[1], heat) if planes is not None else 0
+    _need(heat, torch.float32, who + ".heat", 4)
+    _need_pts(pts, who + ".pts")
+    if tuple(pts.shape[:2]) != tuple(heat.shape[:2]) or pts.device != heat.device:
+        raise HkpError("%s: pts %s on %s does not go with heat %s on %s"
+                       % (who, tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
+    if heat.numel() == 0 or not float(sigma) > 0:
+        raise HkpError("%s: empty heat or sigma %s" % (who, sigma))
+    return topk
+
+
 def _uv_as_pts(heat, uv):
     """uv [N,K,2] as pts [N,K,1,3]: each label one present instance."""
     _need(heat, torch.float32, "heat_loss.heat", 4)
@@ -1510,13 +1527,7 @@ def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True,
             raise HkpError("heat_loss: norm %r needs kind 'qfl' or instance labels (heat_loss_multi)" % (norm,))
         if target is not None:
             raise HkpError("heat_loss: kind 'qfl' recomputes its target from uv; a dense target is not supported")
-        _need(heat, torch.float32, "heat_loss.heat", 4)
-        _need(uv, torch.float32, "heat_loss.uv", 3)
-        n, k = heat.shape[:2]
-        if tuple(uv.shape) != (n, k, 2):
-            raise HkpError("heat_loss: uv must be [N,K,2]")
-        pts = torch.cat([uv, torch.ones_like(uv[..., :1])], -1).reshape(n, k, 1, 3)
-        return heat_loss_multi(heat, pts, sigma, kind, "zero", want_grad, beta=beta, norm=norm)
+        return heat_loss_multi(heat, _uv_as_pts(heat, uv), sigma, kind, "zero", want_grad, beta=beta, norm=norm)
     _need(heat, torch.float32, "heat_loss.heat", 4)
     n, k, H, W = heat.shape
     if target is not None:
@@ -1555,17 +1566,8 @@ def heat_loss_planes(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=
     from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
                        HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
     beta = _loss_choice("heat_loss_planes", kind, norm, beta)
-    if absent not in ABSENT_MODES:
-        raise HkpError("heat_loss_planes: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
-    topk = _planes_choice("heat_loss_planes", weights, topk, heat)
-    _need(heat, torch.float32, "heat_loss_planes.heat", 4)
-    _need_pts(pts, "heat_loss_planes.pts")
+    topk = _multi_loss_args("heat_loss_planes", heat, pts, sigma, absent, (weights, topk))
     n, k, H, W = heat.shape
-    if tuple(pts.shape[:2]) != (n, k) or pts.device != heat.device:
-        raise HkpError("heat_loss_planes: pts %s on %s does not go with heat %s on %s"
-                       % (tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
-    if heat.numel() == 0 or not float(sigma) > 0:
-        raise HkpError("heat_loss_planes: empty heat or sigma %s" % (sigma,))
     ws = torch.empty(lib().hkp_heat_loss_planes_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
     loss = torch.empty((), device=heat.device, dtype=torch.float64)
     dheat = torch.empty_like(heat) if want_grad else None
@@ -1598,16 +1600,8 @@ def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=T
         return heat_loss_planes(heat, pts, sigma, kind, absent, want_grad, beta=beta, norm=norm, weights=weights,
                                 topk=topk)[:2]
     beta = _loss_choice("heat_loss_multi", kind, norm, beta)
-    if absent not in ABSENT_MODES:
-        raise HkpError("heat_loss_multi: unknown absent %r (known: %s)" % (absent, ", ".join(ABSENT_MODES)))
-    _need(heat, torch.float32, "heat_loss_multi.heat", 4)
-    _need_pts(pts, "heat_loss_multi.pts")
+    _multi_loss_args("heat_loss_multi", heat, pts, sigma, absent)
     n, k, H, W = heat.shape
-    if tuple(pts.shape[:2]) != (n, k) or pts.device != heat.device:
-        raise HkpError("heat_loss_multi: pts %s on %s does not go with heat %s on %s"
-                       % (tuple(pts.shape), pts.device, tuple(heat.shape), heat.device))
-    if heat.numel() == 0 or not float(sigma) > 0:
-        raise HkpError("heat_loss_multi: empty heat or sigma %s" % (sigma,))
     ws = torch.empty(lib().hkp_heat_loss_multi_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
     loss = torch.empty((), device=heat.device, dtype=torch.float64)
     dheat = torch.empty_like(heat) if want_grad else None
