@@ -38,6 +38,11 @@ writes preds/metrics.json: KeypointMetrics.compute()'s dict (nan as null).  With
 RESIZE set the peaks are mapped to each source image's pixels before the matching and
 the labels are in source pixels, so EVAL's thresholds are distances in SOURCE pixels.
 Everything else written is what it is without EVAL.
+
+PEAKS and EVAL may each hold "tta": a dict of hkp.tta.TestTimeAugmentation's keyword
+arguments.  The forward above is then view 0, every other view one more forward of the
+same image, and that decode reads the merged logits (ops.logits_merge) instead of the
+one forward's; keypoints.npy and the overlays still come from the plain forward.
 """
 import os
 import sys
@@ -83,10 +88,20 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
     lo, hi = parallel.shard_range(len(files), parallel.rank(), parallel.world())
     kps, pks, cts = [], [], []
     npk = int(PEAKS.get("max_peaks", 4)) if PEAKS is not None else 0
-    metrics = eval_kw = None
+    from hkp.tta import split_config
+    peaks_kw, peaks_tta = split_config(PEAKS)
+    metrics = eval_kw = eval_tta = None
     if EVAL is not None and label_dir:
         from hkp.metrics import from_config, load_labels
         metrics, eval_kw = from_config(EVAL, NUM_KEYPOINTS, device="cuda")
+        eval_tta = eval_kw.pop("tta", None)
+
+    def merged(tta, x, low):                         # the views' forwards beside the plain one (view 0)
+        if tta is None:
+            return low
+        return tta.run(x, lambda xv: net.keypoints_forward(keypoints.resnet.net, xv, NUM_KEYPOINTS, heat=False,
+                                                           argmax=False, pol=keypoints.policy, upsample=False)[2],
+                       low0=low)
     for i in range(lo, hi):
         img = imread_bgr(os.path.join(image_dir, files[i]))
         print(img.shape)
@@ -104,13 +119,15 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
                 heatmap, kp, low = net.keypoints_forward(keypoints.resnet.net, img_t.view(-1, *img_t.shape),
                                                          NUM_KEYPOINTS, heat=True, argmax=True, pol=keypoints.policy)
             if PEAKS is not None:
-                pk, ct = ops.heat_peaks(low, IMG_HEIGHT, IMG_WIDTH, **PEAKS)
+                pk, ct = ops.heat_peaks(merged(peaks_tta, img_t.view(-1, *img_t.shape), low), IMG_HEIGHT, IMG_WIDTH,
+                                        **peaks_kw)
                 if plan is not None:                 # (x, y) of the used slots -> the source image's pixels
                     pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
                 pks.append(pk[0])
                 cts.append(ct[0])
             if metrics is not None:                  # EVAL's own decode, matched to this image's labels
-                pk, ct = ops.heat_peaks(low, IMG_HEIGHT, IMG_WIDTH, **eval_kw)
+                pk, ct = ops.heat_peaks(merged(eval_tta, img_t.view(-1, *img_t.shape), low), IMG_HEIGHT, IMG_WIDTH,
+                                        **eval_kw)
                 if plan is not None:
                     pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
                 lab = load_labels(os.path.join(label_dir, os.path.splitext(files[i])[0] + ".npy"), NUM_KEYPOINTS)

@@ -56,6 +56,14 @@ hkp.synth.CableScenes —: train.py's main() needs no data/ directory, both sets
 cable scenes rendered on the GPU, hkp_synth_cables_u8, with instance labels [K,M,3] of M =
 "instances" slots; the train set draws new scenes every epoch, the test set is fixed and
 comes from seed + 1; NUM_KEYPOINTS must equal the number of classes).
+PEAKS and EVAL each also take "tta": a dict of hkp.tta.TestTimeAugmentation's keyword
+arguments, e.g. {"hflip": True, "flip_pairs": ((0, 1),), "mode": "prob"} — test-time
+augmentation: the decode then reads the logits of several views (mirrored, rescaled), one
+forward each, merged on the stride-8 lattice by one launch, hkp_logits_merge.  The plain
+forward is view 0 and still gives `test loss:`, keypoints.npy and the overlays; the other
+views are extra forwards under the same no_grad (in train-mode BN each takes its own batch
+statistics and moves the running ones).  Scaled views ("scales") need uint8 NHWC batches:
+analysis.py and a test set of fp32 tensors take flips only.  An unknown key raises.
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480

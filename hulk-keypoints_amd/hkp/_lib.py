@@ -129,6 +129,21 @@ class SynthScene(ctypes.Structure):
 
 assert ctypes.sizeof(SynthSeg) == 64 and ctypes.sizeof(SynthScene) == 64
 
+# the test-time augmentation merge's ABI (include/hulkkp.h)
+HKP_MERGE_LOGIT, HKP_MERGE_PROB = 0, 1
+HKP_MERGE_MAX_VIEWS = 8
+
+
+class MergeView(ctypes.Structure):
+    """hkp_merge_view (hkp_logits_merge): where one view's logits lie in the packed
+    buffer, its lattice, the per-axis map base node -> view node and its weight."""
+    _fields_ = [("off", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ay", ctypes.c_double),
+                ("by", ctypes.c_double), ("ax", ctypes.c_double), ("bx", ctypes.c_double),
+                ("weight", ctypes.c_double), ("reserved", ctypes.c_int64)]
+
+
+assert ctypes.sizeof(MergeView) == 64
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -253,6 +268,8 @@ SIGNATURES = {
     # procedural cable scenes (scenes_host / segs_host: host copies, validated; scenes / segs: device copies)
     "hkp_synth_cables_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, ctypes.POINTER(SynthScene), _P,
                                            ctypes.POINTER(SynthSeg), _P, _I32, _P]),
+    # test-time augmentation: views' logits merged on the base lattice (table: MergeView records, perm: device)
+    "hkp_logits_merge": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

@@ -97,15 +97,22 @@ def compute_from_state(hist, totals, thresholds):
             "overall": overall}
 
 
-EVAL_KEYS = ("thresholds", "bins", "max_peaks", "radius", "threshold")
+EVAL_KEYS = ("thresholds", "bins", "max_peaks", "radius", "threshold", "tta")
 
 
 def from_config(cfg, num_keypoints, device=None):
     """config.EVAL (a dict with any of EVAL_KEYS) → (KeypointMetrics, the keyword
-    arguments of KeypointsGauss.predict_peaks)."""
+    arguments of KeypointsGauss.predict_peaks).  With "tta" (a dict of
+    hkp.tta.TestTimeAugmentation's keyword arguments) they hold the object as
+    "tta"; without it there is no such entry."""
     unknown = sorted(set(cfg) - set(EVAL_KEYS))
     if unknown:
         raise ValueError("EVAL: unknown keys %s (known: %s)" % (unknown, ", ".join(EVAL_KEYS)))
+    if cfg.get("tta") is not None:
+        from .tta import from_config as tta_from_config
+        metrics, peak_kw = from_config({k: v for k, v in cfg.items() if k != "tta"}, num_keypoints, device)
+        peak_kw["tta"] = tta_from_config(cfg["tta"])
+        return metrics, peak_kw
     metrics = KeypointMetrics(num_keypoints, cfg.get("thresholds", (2, 4, 8, 16)), bins=cfg.get("bins", 1024),
                               device=device)
     peak_kw = {"max_peaks": int(cfg.get("max_peaks", 4)), "radius": int(cfg.get("radius", 1)),

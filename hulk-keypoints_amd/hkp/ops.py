@@ -710,6 +710,68 @@ def heat_peaks(low, H, W, max_peaks=4, radius=1, threshold=0.0):
     return peaks, counts
 
 
+# the packed views of logits_merge, one flat fp32 buffer per (device, stream), grown
+# on demand: launches sharing a stream never run concurrently
+_merge_buf = {}
+
+
+def logits_merge(lows, plan_or_table, perm=None, mode="prob", out=None):
+    """Test-time augmentation's merge (csrc/tta.hip): lows, one fp32 [N,K,h_v,w_v]
+    tensor per view, and the launch's hkp.tta.MergePlan — or its pieces: a sequence
+    of (h_v, w_v, ay, by, ax, bx, weight) per view with perm, integers [views, K],
+    both on the host — → fp32 [N,K,h,w] on the plan's base lattice; the definition
+    is hkp_logits_merge's (include/hulkkp.h).  mode: "prob" or "logit".  The views
+    are copied into one reused flat buffer (at most 8 small copies), then one launch
+    on the current stream; the plan's table and perm are uploaded once.  out: an
+    fp32 tensor of the result's shape to write into (any 4-byte alignment)."""
+    from . import tta
+    if mode not in tta.MODES:
+        raise HkpError("logits_merge: unknown mode %r (known: %s)" % (mode, ", ".join(tta.MODES)))
+    lows = list(lows)
+    if not 1 <= len(lows) <= tta.HKP_MERGE_MAX_VIEWS:
+        raise HkpError("logits_merge: %d views outside 1..%d" % (len(lows), tta.HKP_MERGE_MAX_VIEWS))
+    for i, t in enumerate(lows):
+        _need(t, torch.float32, "logits_merge.lows[%d]" % i, 4)
+        if t.device != lows[0].device or tuple(t.shape[:2]) != tuple(lows[0].shape[:2]) or t.numel() == 0:
+            raise HkpError("logits_merge: view %d is %s on %s, view 0 %s on %s: need non-empty views of one batch on "
+                           "one device" % (i, tuple(t.shape), t.device, tuple(lows[0].shape), lows[0].device))
+    n, k = lows[0].shape[:2]
+    if isinstance(plan_or_table, tta.MergePlan):
+        plan = plan_or_table
+        if perm is not None:
+            raise HkpError("logits_merge: a MergePlan carries its own perm")
+    else:
+        if perm is None:
+            raise HkpError("logits_merge: a view table needs perm")
+        plan = tta.MergePlan(n, k, lows[0].shape[2:] if out is None else out.shape[2:], plan_or_table, perm)
+    if (plan.n, plan.k, plan.n_views) != (n, k, len(lows)):
+        raise HkpError("logits_merge: the plan is for %d views of [%d,%d,..], got %d of [%d,%d,..]"
+                       % (plan.n_views, plan.n, plan.k, len(lows), n, k))
+    for i, t in enumerate(lows):
+        if tuple(t.shape[2:]) != plan.lattices[i]:
+            raise HkpError("logits_merge: view %d has lattice %s, the plan %s" % (i, tuple(t.shape[2:]), plan.lattices[i]))
+    h, w = plan.hw
+    dev = lows[0].device
+    if out is None:
+        out = torch.empty((n, k, h, w), device=dev, dtype=torch.float32)
+    else:
+        _need(out, torch.float32, "logits_merge.out", 4)
+        if tuple(out.shape) != (n, k, h, w) or out.device != dev:
+            raise HkpError("logits_merge: out must be %s on %s, got %s on %s" % ((n, k, h, w), dev, tuple(out.shape),
+                                                                               out.device))
+    st = torch.cuda.current_stream(dev)
+    key = (st.device_index, st.cuda_stream)
+    buf = _merge_buf.get(key)
+    if buf is None or buf.numel() < plan.total:
+        buf = _merge_buf[key] = torch.empty(plan.total, device=dev, dtype=torch.float32)
+    for r, t in zip(plan.records, lows):
+        buf[r.off:r.off + t.numel()].copy_(t.reshape(-1))
+    table, perm_d = plan.device_arrays(dev)
+    call("hkp_logits_merge", n, k, h, w, plan.n_views, tta.MODES[mode], _ptr(buf), _ptr(table), _ptr(perm_d), _ptr(out),
+         ctypes.c_void_p(st.cuda_stream))
+    return out
+
+
 # two-level finalize (hkp_bn_finalize_ws) from this many partial tiles on: C4 +2.2 %
 # (R50 C = 2048 convs, 4,800+ tiles); at 300-1,200 tiles (C2 layer2-4, the C3
 # shard) the one-kernel merge already fills the chip and its single launch won

@@ -239,32 +239,35 @@ def predict_keypoints_dp(model, x_shard, heat=False, sync=False, group=None, glo
 
 @torch.no_grad()
 def predict_peaks_dp(model, x_shard, max_peaks=4, radius=1, threshold=0.0, sync=False, group=None,
-                     global_batch=None):
+                     global_batch=None, tta=None):
     """Each rank's shard through the fused forward and the multi-peak decode
     (KeypointsGauss.predict_peaks); peaks and counts gathered.  sync / group /
-    global_batch: as for predict_keypoints_dp.
+    global_batch: as for predict_keypoints_dp.  tta (hkp.tta.TestTimeAugmentation, the
+    same on every rank): every rank makes the same forwards, one per view, in the
+    same order, so SyncBN's collectives line up view by view.
     Returns (global float32 [B, K, max_peaks, 3] (x, y, score), global int32 [B, K])."""
     pol = model.policy.with_(sync_bn=True, sync_group=group) if sync else model.policy
     if sync:
         ShardCheck(group)(x_shard.shape[0], global_batch)
-    peaks, counts = model.predict_peaks(x_shard, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=pol)
+    peaks, counts = model.predict_peaks(x_shard, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=pol,
+                                        tta=tta)
     return gather_peaks(peaks, counts, group)
 
 
 @torch.no_grad()
 def evaluate_dp(model, x_shard, labels_shard, metrics, max_peaks=4, radius=1, threshold=0.0, sync=False, group=None,
-                global_batch=None):
+                global_batch=None, tta=None):
     """Each rank's shard through the fused forward, the multi-peak decode and the
     on-device matching against its own labels (KeypointsGauss.evaluate), added into
     this rank's `metrics` (hkp.metrics.KeypointMetrics).  No collective per batch:
     nothing is gathered; the caller sums the ranks' integer accumulators once, at the
-    end of the pass, with metrics.all_reduce(group).  sync / group / global_batch: as
-    for predict_peaks_dp.  Returns this shard's (peaks, counts)."""
+    end of the pass, with metrics.all_reduce(group).  sync / group / global_batch / tta:
+    as for predict_peaks_dp.  Returns this shard's (peaks, counts)."""
     pol = model.policy.with_(sync_bn=True, sync_group=group) if sync else model.policy
     if sync:
         ShardCheck(group)(x_shard.shape[0], global_batch)
     return model.evaluate(x_shard, labels_shard, metrics, max_peaks=max_peaks, radius=radius, threshold=threshold,
-                          policy=pol)
+                          policy=pol, tta=tta)
 
 
 # ---- SyncBN (SURVEY §8(e), caveat D5) ----------------------------------------

@@ -60,7 +60,26 @@ class KeypointsGauss(nn.Module):
         return yx
 
     @torch.no_grad()
-    def predict_peaks(self, x, max_peaks=4, radius=1, threshold=0.0, policy=None):
+    def lowres_logits(self, x, tta=None, policy=None):
+        """The low-res logits [B,K,h,w] fp32 the peak decode reads (not in the
+        reference).  tta=None: those of one forward.  tta: a
+        hkp.tta.TestTimeAugmentation — one forward per view, in the views' order
+        (view 0 is x itself), then one launch that merges them on x's own lattice
+        (ops.logits_merge).  Every view is a forward like any other: in train-mode
+        BN it takes its own batch statistics and moves the running ones; under
+        eval() nothing is written.  Scaled views need a uint8 NHWC batch."""
+        pol = policy or self.policy
+
+        def fwd(xv):
+            return net.keypoints_forward(self.resnet.net, xv, self.num_keypoints, heat=False, argmax=False, pol=pol,
+                                         upsample=False)[2]
+        if tta is None:
+            return fwd(x)
+        tta.check_input(x)
+        return tta.run(x, fwd)
+
+    @torch.no_grad()
+    def predict_peaks(self, x, max_peaks=4, radius=1, threshold=0.0, policy=None, tta=None):
         """Multi-peak decode (not in the reference): (peaks float32 [B,K,max_peaks,3],
         counts int32 [B,K]) — per heatmap the up to max_peaks best local maxima with
         score >= threshold, best first, no two within Chebyshev distance `radius` of
@@ -69,20 +88,22 @@ class KeypointsGauss(nn.Module):
         positions in input pixels, score the heatmap's value at the node; unused
         slots (-1, -1, 0).  Same inputs as predict_keypoints (fp32 NCHW or uint8
         NHWC); decoded from the low-res logits (ops.heat_peaks): no heatmap is
-        allocated and no upsample launch is made."""
+        allocated and no upsample launch is made.  tta: a
+        hkp.tta.TestTimeAugmentation — the peaks of the merged views' logits
+        (lowres_logits), in x's own pixels."""
         from hkp import ops
-        _, _, low = net.keypoints_forward(self.resnet.net, x, self.num_keypoints, heat=False, argmax=False,
-                                          pol=policy or self.policy, upsample=False)
+        low = self.lowres_logits(x, tta=tta, policy=policy)
         H, W = net.image_nchw_shape(x)[2:]
         return ops.heat_peaks(low, H, W, max_peaks=max_peaks, radius=radius, threshold=threshold)
 
     @torch.no_grad()
-    def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None):
+    def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None, tta=None):
         """predict_peaks, then one launch that matches the peaks to `labels` ([B,K,M,3]
         (u, v, flag) or [B,K,2], in input pixels, on the device) and adds the outcome
         into `metrics` (hkp.metrics.KeypointMetrics); no host synchronisation.
-        Returns the (peaks, counts) of predict_peaks."""
-        peaks, counts = self.predict_peaks(x, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=policy)
+        Returns the (peaks, counts) of predict_peaks.  tta: as for predict_peaks."""
+        peaks, counts = self.predict_peaks(x, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=policy,
+                                           tta=tta)
         metrics.update(peaks, counts, labels)
         return peaks, counts
 

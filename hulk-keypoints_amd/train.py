@@ -142,8 +142,13 @@ def eval_forward(sample_batched, model, metrics, peak_kw):
     loss (from its heatmaps) and, from its low-res logits, the decoded peaks, which one
     more launch matches to the batch's labels and adds into `metrics`
     (hkp.metrics.KeypointMetrics); no host synchronisation beyond the caller's
-    loss.item().  The labels must be (u, v) [B,K,2] or instances [B,K,M,3]."""
+    loss.item().  The labels must be (u, v) [B,K,2] or instances [B,K,M,3].
+    With EVAL's "tta" (peak_kw["tta"], a hkp.tta.TestTimeAugmentation) that forward
+    still gives the test loss and is view 0; the other views are extra forwards under
+    the same no_grad, and the peaks are those of the merged logits."""
     img, gt = sample_batched
+    peak_kw = dict(peak_kw)
+    tta = peak_kw.pop("tta", None)
     dense = (img.shape[0], model.num_keypoints) + tuple(net.image_nchw_shape(img)[2:])
     if tuple(gt.shape) == dense or not (gt.dim() == 3 or (gt.dim() == 4 and gt.shape[-1] == 3)):
         raise ops.HkpError("EVAL needs point labels ([B,K,2] or [B,K,M,3]), not dense targets %s: build the test "
@@ -154,6 +159,10 @@ def eval_forward(sample_batched, model, metrics, peak_kw):
                                              pol=model.policy)
         loss = _loss(heat, gt)
         H, W = net.image_nchw_shape(img)[2:]
+        if tta is not None:
+            low = tta.run(img, lambda xv: net.keypoints_forward(model.resnet.net, xv, model.num_keypoints, heat=False,
+                                                                argmax=False, pol=model.policy, upsample=False)[2],
+                          low0=low)
         peaks, counts = ops.heat_peaks(low, H, W, **peak_kw)
         metrics.update(peaks, counts, gt.cuda().float().contiguous())
     return loss

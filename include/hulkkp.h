@@ -1130,6 +1130,67 @@ int hkp_synth_cables_u8(int32_t n, int32_t h, int32_t w, uint8_t* img_out, const
                         const hkp_synth_scene* scenes, const hkp_synth_seg* segs_host, const hkp_synth_seg* segs,
                         int32_t nsegs, hkp_stream_t stream);
 
+/* ==================================== test-time augmentation: view merge ==== */
+/* The low-res logits of several views of one batch (the input as it is, flipped,
+ * rescaled: one forward each) merged into logits on the base view's stride-8
+ * lattice, in one launch (csrc/tta.hip); hkp_heat_peaks reads the result as it
+ * reads one forward's.  Not in the reference.
+ *
+ *  packed  the views' logits, one after the other in one flat fp32 buffer: view v
+ *          is [n][k][h_v][w_v], contiguous, at element offset off_v.
+ *  table   `views` hkp_merge_view records in device memory (below).
+ *  perm    int32 [views][k] in device memory: the channel of view v that feeds
+ *          output channel c is perm[v][c] (the flip pairs).
+ *  out     [n][k][h][w] fp32; must not overlap packed.
+ *
+ * For output node (i, j) of plane (b, c) and view v, all in fp64, no fused
+ * multiply-add, the views in table order (tests/_tta_ref.py restates it in numpy):
+ *  coordinates  cy = ay*i + by (one multiply, then one add), clamped to
+ *               [0, h_v - 1]; i0 = floor(cy), fy = cy - i0, i1 = min(i0 + 1, h_v - 1);
+ *               the same along x with (ax, bx), j and w_v.
+ *  sample       with z the fp32 logits of view v, image b, channel perm[v][c]:
+ *                 top = z[i0][j0] + fx*(z[i0][j1] - z[i0][j0])
+ *                 bot = z[i1][j0] + fx*(z[i1][j1] - z[i1][j0])
+ *                 z_v = top + fy*(bot - top)
+ *               A tap whose weight is exactly 0 is not read: fx == 0 gives
+ *               top = z[i0][j0] and bot = z[i1][j0], fy == 0 gives z_v = top.  A flip
+ *               (a = -1, b = dim - 1) is therefore an exact copy, even beside a NaN or
+ *               an infinity.  (An infinity in a tap that IS read with a fractional
+ *               weight follows the formula: inf - inf is NaN.)
+ *  HKP_MERGE_LOGIT  out = (float) sum_v weight_v * z_v; the sum starts with view 0's
+ *                   term, not with +0, so one identity view returns its input's bits
+ *                   (-0 included)
+ *  HKP_MERGE_PROB   zc = min(max(z_v, -700), 700), a NaN stays NaN;
+ *                   p = sum_v weight_v / (1 + exp(-zc)),  q = sum_v weight_v / (1 + exp(zc));
+ *                   out = (float)(log p - log q): the logit of the weighted mean
+ *                   probability, both tails summed so that scores near 1 keep
+ *                   their precision.
+ * One thread per output element (per 4 of a row, stored as 16 bytes, where
+ * w % 4 == 0 and out is 16-byte aligned), grid-stride over a capped grid; no LDS, no
+ * atomics, no workspace: the same input gives the same bits.
+ * Checked on the host arguments alone, before anything is written: n, k, h, w >= 1,
+ * 1 <= views <= HKP_MERGE_MAX_VIEWS, mode, non-null pointers, packed / perm / out
+ * 4-byte and table 8-byte aligned; anything else is HKP_ERR_BAD_ARG.  The table's
+ * contents (off, 1 <= h_v, w_v, finite coefficients, 0 <= perm < k, every view inside
+ * packed) are the caller's contract, as for the warp and resample plans; tap indices
+ * and the channel are clamped into range before an address is formed. */
+#define HKP_MERGE_LOGIT 0
+#define HKP_MERGE_PROB 1
+#define HKP_MERGE_MAX_VIEWS 8
+
+typedef struct hkp_merge_view {   /* 64 bytes */
+    int64_t off;           /* element offset of the view's [n][k][h][w] logits in packed */
+    int32_t h, w;          /* the view's lattice                                         */
+    double ay, by;         /* base row i    -> view row    ay*i + by                     */
+    double ax, bx;         /* base column j -> view column ax*j + bx                     */
+    double weight;         /* the view's share of the sum                                */
+    int64_t reserved;      /* 0 */
+} hkp_merge_view;
+
+int hkp_logits_merge(int32_t n, int32_t k, int32_t h, int32_t w, int32_t views, int32_t mode,
+                     const float* packed, const void* table, const int32_t* perm,
+                     float* out, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
