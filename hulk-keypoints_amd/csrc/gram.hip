@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(int C, int TC, int til
     const long per = (long)TC * TC, nel = per * tiles;
     const int v = threadIdx.x % NV, g = threadIdx.x / NV;
     const long gid = (long)blockIdx.x * NV + v;
-    const double inv = 1.0 / (double)M;
+    const double dm = (double)M;       // divided by, not multiplied with 1 / M: one rounding per value
     const int k_lo = (int)((long)splits * g / SG), k_hi = (int)((long)splits * (g + 1) / SG);
     auto split_sum = [&](const float* p, long st) -> double {
         double s = 0.0;
@@ -263,11 +263,11 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(int C, int TC, int til
     }
     if (!live) return;
     if (is_e) {
-        const double val = s * inv;
+        const double val = s / dm;
         e2[(long)ci * C + cj] = val;
         e2[(long)cj * C + ci] = val;
     } else {
-        mu[gid - nel] = s * inv;
+        mu[gid - nel] = s / dm;
     }
 }
 
