@@ -43,6 +43,14 @@ PEAKS and EVAL may each hold "tta": a dict of hkp.tta.TestTimeAugmentation's key
 arguments.  The forward above is then view 0, every other view one more forward of the
 same image, and that decode reads the merged logits (ops.logits_merge) instead of the
 one forward's; keypoints.npy and the overlays still come from the plain forward.
+
+PEAKS may also hold "groups": {"classes": (class indices), "max_dist": 1.0} (a model trained
+with config.TAGS; not with "tta": tags are not merged across views).  The one forward then
+runs the head over the fc rows 0..2K-1 — the heat channels, and with them everything above,
+are the same bits — and rank 0 also saves preds/peak_groups.npy, int32 [n_images, K,
+max_peaks]: the cable of every peak of peaks.npy, grouped by tag on the GPU
+(ops.peaks_group, what KeypointsGauss.predict_groups returns), -1 for unused slots and
+classes not listed.
 """
 import os
 import sys
@@ -90,6 +98,13 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
     npk = int(PEAKS.get("max_peaks", 4)) if PEAKS is not None else 0
     from hkp.tta import split_config
     peaks_kw, peaks_tta = split_config(PEAKS)
+    groups_kw = peaks_kw.pop("groups", None) if peaks_kw is not None else None
+    grs = []
+    if groups_kw is not None:
+        if peaks_tta is not None:
+            raise ValueError("config.PEAKS: 'groups' does not go with 'tta' (tags are not merged across views)")
+        if set(groups_kw) - {"classes", "max_dist"} or "classes" not in groups_kw:
+            raise ValueError("config.PEAKS['groups'] holds classes and optionally max_dist, got %r" % (groups_kw,))
     metrics = eval_kw = eval_tta = None
     if EVAL is not None and label_dir:
         from hkp.metrics import from_config, load_labels
@@ -117,10 +132,16 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
                 heatmap, kp = keypoints.heatmaps_and_keypoints(img_t.view(-1, *img_t.shape))
             else:                                    # the same forward; its low-res logits feed the peak decode
                 heatmap, kp, low = net.keypoints_forward(keypoints.resnet.net, img_t.view(-1, *img_t.shape),
-                                                         NUM_KEYPOINTS, heat=True, argmax=True, pol=keypoints.policy)
+                                                         NUM_KEYPOINTS, heat=True, argmax=True, pol=keypoints.policy,
+                                                         tags=groups_kw is not None)
+                if groups_kw is not None:            # low_all: heat logits, then the tag maps
+                    low_all, low = low, low[:, :NUM_KEYPOINTS].contiguous()
             if PEAKS is not None:
                 pk, ct = ops.heat_peaks(merged(peaks_tta, img_t.view(-1, *img_t.shape), low), IMG_HEIGHT, IMG_WIDTH,
                                         **peaks_kw)
+                if groups_kw is not None:            # grouped on the network's own frame
+                    grs.append(ops.peaks_group(pk, ct, low_all, IMG_HEIGHT, IMG_WIDTH, groups_kw["classes"],
+                                               max_dist=groups_kw.get("max_dist", 1.0))[0][0])
                 if plan is not None:                 # (x, y) of the used slots -> the source image's pixels
                     pk = plan.invert_peaks(pk.cpu(), ct.cpu()).to(pk.device)
                 pks.append(pk[0])
@@ -144,6 +165,10 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
                                                             device="cuda")
         local_ct = torch.stack(cts) if cts else torch.zeros((0, NUM_KEYPOINTS), dtype=torch.int32, device="cuda")
         all_pk, all_ct = (t.cpu().numpy() for t in parallel.gather_peaks(local_pk, local_ct))
+        if groups_kw is not None:
+            local_gr = torch.stack(grs) if grs else torch.zeros((0, NUM_KEYPOINTS, npk), dtype=torch.int32,
+                                                                device="cuda")
+            all_gr = parallel.gather_groups(local_gr).cpu().numpy()
     if metrics is not None:
         metrics.all_reduce()
     if parallel.rank() == 0:
@@ -156,6 +181,8 @@ def main(model_ckpt="", image_dir="", out_dir="preds", checkpoint_dir="checkpoin
         if PEAKS is not None:
             np.save(os.path.join(out_dir, "peaks.npy"), all_pk)
             np.save(os.path.join(out_dir, "peak_counts.npy"), all_ct)
+            if groups_kw is not None:
+                np.save(os.path.join(out_dir, "peak_groups.npy"), all_gr)
     if own_group:
         dist.destroy_process_group()
     return all_kp

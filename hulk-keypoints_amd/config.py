@@ -64,6 +64,15 @@ forward is view 0 and still gives `test loss:`, keypoints.npy and the overlays; 
 views are extra forwards under the same no_grad (in train-mode BN each takes its own batch
 statistics and moves the running ones).  Scaled views ("scales") need uint8 NHWC batches:
 analysis.py and a test set of fp32 tensors take flips only.  An unknown key raises.
+TAGS (None: nothing changes; a dict such as {"classes": ("cap", "tail"), "weight": 1e-3, "pull":
+1.0, "push": 1.0} — classes as indices or as names of SYNTH["classes"] —: associative-embedding
+tags, which keypoints belong to one cable.  train.py's train loop steps hkp.train.Trainer(tags=):
+fc row K + c becomes the tag map of class c (2 * NUM_KEYPOINTS <= 16), trained by hkp_tag_loss
+with instance labels whose slot m is cable m, and fit() prints one more line, `train tag loss:
+total pull push`, after `train loss:`).  PEAKS also takes "groups": {"classes": (class indices),
+"max_dist": 1.0}: analysis.py then also writes preds/peak_groups.npy, int32 [n_images, K,
+max_peaks], the cable of every peak of peaks.npy (KeypointsGauss.predict_groups; -1: none); it
+does not go with "tta".
 """
 NUM_KEYPOINTS = 4
 IMG_HEIGHT = 480
@@ -90,3 +99,4 @@ MAX_GRAD_NORM = None
 EMA_DECAY = None
 CLASS_LOSS = False
 SYNTH = None
+TAGS = None

@@ -7,5 +7,6 @@ autograd  the autograd.Function that runs the backward kernels
 resample  antialiased resize of uint8 images of any size (axis tables, plans, label maps)
 metrics   keypoint evaluation on the device (KeypointMetrics: PCK, precision, AP, mean error)
 tta       test-time augmentation: views of a batch and the merge of their low-res logits
+grouping  associative-embedding tags: default group labels and the pairing scores
 """
 from ._lib import HkpError, LIB_PATH, lib, version  # noqa: F401

@@ -270,6 +270,13 @@ SIGNATURES = {
                                            ctypes.POINTER(SynthSeg), _P, _I32, _P]),
     # test-time augmentation: views' logits merged on the base lattice (table: MergeView records, perm: device)
     "hkp_logits_merge": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    # associative-embedding tags (tags: channel k of image 0 of low_all, batch stride in elements;
+    # order: int32 array on the host)
+    "hkp_tag_loss_workspace": (_I64, [_I32]),
+    "hkp_tag_loss": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _F, _F, _F, _P, _P, _P,
+                                    _P]),
+    "hkp_peaks_group": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), _F, _P, _P,
+                                       _P, _I64, _P, _P, _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

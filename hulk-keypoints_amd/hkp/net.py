@@ -564,15 +564,25 @@ def fc_rows(resnet, k):
     return w.reshape(w.shape[0], -1)[:k], resnet.fc.bias[:k]
 
 
-def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, pol=None, upsample=True):
+def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, pol=None, upsample=True, tags=False):
     """Fused K-channel head: heat = sigmoid(upsample(fc[:K](feat)))  (model.py:19-22).
     pol: the execution policy (a trace carries its own).  upsample=False (the peak
-    decode, which reads `low` alone): no upsample launch, (None, None, low)."""
+    decode, which reads `low` alone): no upsample launch, (None, None, low).
+    tags=True (associative embedding, hkp.grouping; 2K <= 16): the head runs over the
+    fc rows 0..2K-1 in the same launch and the third value is low_all [B,2K,h,w], heat
+    logits then tag maps; every row of the head kernels is computed on its own, so the
+    heat channels are the bits of the K-row launch.  The upsample, sigmoid and argmax
+    see the heat channels only (a contiguous copy); trace.head keeps low_all."""
     pol = trace.policy if trace is not None else resolve(pol)
     if trace is not None and pol.precision in INFERENCE_ONLY:
         raise ops.HkpError("precision %r is inference-only; train with 'f16x3' or 'fp32'" % pol.precision)
-    w, b = fc_rows(resnet, k)
-    if trace is None and pol.fused_head and ops.head_fusable(_feat_channels(resnet), k):
+    rows = k
+    if tags:
+        if not 1 <= 2 * k <= 16:
+            raise ops.HkpError("keypoints_forward: tags take head rows K..2K-1 of at most 16 (K = %d)" % k)
+        rows = 2 * k
+    w, b = fc_rows(resnet, rows)
+    if trace is None and pol.fused_head and ops.head_fusable(_feat_channels(resnet), rows):
         feat, low = None, backbone_forward(resnet, x_nchw, None, head=(w, b), pol=pol)
     else:
         feat = backbone_forward(resnet, x_nchw, trace, pol=pol)
@@ -582,9 +592,10 @@ def keypoints_forward(resnet, x_nchw, k, heat=True, argmax=False, trace=None, po
             raise ops.HkpError("keypoints_forward: a traced (training) forward needs the upsample")
         return None, None, low
     H, W = image_nchw_shape(x_nchw)[2:]
-    hm, yx = ops.upsample_sigmoid(low, H, W, heat=heat, argmax=argmax)
+    low_heat = low[:, :k].contiguous() if tags else low
+    hm, yx = ops.upsample_sigmoid(low_heat, H, W, heat=heat, argmax=argmax)
     if trace is not None:
-        trace.head = dict(feat=feat, low=low, heat=hm, k=k, H=H, W=W)
+        trace.head = dict(feat=feat, low=low, heat=hm, k=k, H=H, W=W, tags=bool(tags))
     return hm, yx, low
 
 
@@ -834,14 +845,27 @@ def stem_backward(resnet, st, g_pool, grads, pol=None):
                                               _i(c.dilation), layout="nchw"))
 
 
-def keypoints_backward(resnet, trace, dheat, grads):
+def keypoints_backward(resnet, trace, dheat, grads, dtag=None):
     """dL/dheat → every parameter gradient (model.py:19-22 backward), under the
-    policy the forward ran with (trace.policy)."""
+    policy the forward ran with (trace.policy).  dtag [B,K,h,w] (ops.tag_loss; a
+    forward with tags=True only): the gradient of the tag maps, concatenated to
+    dlow before the fc backward, which then covers the fc rows 0..2K-1."""
     pol = trace.policy
     hd = trace.head
     k = hd["k"]
     feat, low = hd["feat"], hd["low"]
+    # checked before anything is launched
+    if hd.get("tags", False) != (dtag is not None):
+        raise ops.HkpError("keypoints_backward: dtag goes with a forward that ran with tags=True, and only with it")
+    if dtag is not None:
+        want = (low.shape[0], k, low.shape[2], low.shape[3])
+        if tuple(dtag.shape) != want or dtag.dtype != torch.float32 or dtag.device != low.device:
+            raise ops.HkpError("keypoints_backward: dtag %s %s on %s does not go with dlow float32 %s on %s"
+                               % (dtag.dtype, tuple(dtag.shape), dtag.device, want, low.device))
     dlow = ops.head_bwd(dheat.contiguous(), hd["heat"], low.shape[2], low.shape[3])
+    if dtag is not None:
+        dlow = torch.cat([dlow, dtag], 1)
+        k = 2 * k
     w, _ = fc_rows(resnet, k)
     dfeat, dw, db = ops.head_fc_bwd(dlow, feat, w)
     fcw, fcb = resnet.fc.weight, resnet.fc.bias

@@ -1747,6 +1747,132 @@ def peaks_match(peaks, counts, pts, thresholds, hist, totals, bins=1024, outputs
     return (pm, gm, gd) if outputs else None
 
 
+TAGS_MAX_K = 8                        # tags are head rows K..2K-1 of at most 16
+TAGS_MAX_GROUPS = 32                  # label group ids of hkp_tag_loss
+
+
+def _tag_planes(who, low_all):
+    """K and the lattice of low_all [N,2K,h,w] (heat logits, then the tag planes, which the
+    kernels read in place from channel K on with the batch stride 2K*h*w)."""
+    if not isinstance(low_all, torch.Tensor) or low_all.dim() != 4:
+        raise HkpError("%s: low_all must be a float32 tensor [N,2K,h,w]" % who)
+    n, k2, h, w = low_all.shape
+    if k2 % 2 or not 1 <= k2 // 2 <= TAGS_MAX_K or min(n, h, w) < 1:
+        raise HkpError("%s: low_all %s: need [N,2K,h,w] with 1 <= K <= %d (the tag map of class c is head row K + c "
+                       "of at most 16) and non-empty planes" % (who, tuple(low_all.shape), TAGS_MAX_K))
+    return n, k2 // 2, h, w
+
+
+def _tag_weight(who, name, v):
+    v = ctypes.c_float(float(v)).value
+    if not (v >= 0.0 and v != float("inf")):
+        raise HkpError("%s: %s must be finite and >= 0, got %r" % (who, name, v))
+    return v
+
+
+def _tags_ptr(low_all, k):
+    return ctypes.c_void_p(low_all.data_ptr() + 4 * k * low_all.shape[2] * low_all.shape[3])
+
+
+def tag_loss(low_all, pts, gid, H, W, scale, pull=1.0, push=1.0, want_grad=True, dtag=None):
+    """Associative-embedding loss on the tag planes of low_all [N,2K,h,w] (channels K..2K-1,
+    read in place) at the labelled points pts float32 [N,K,M,3] (u, v, flag) grouped by gid
+    int32 [N,K,M] (a slot takes part when flag > 0 and 0 <= gid < 32; hkp.grouping.slot_groups
+    builds the default) → (out3 float64 [3] = (total, mean pull, mean push) with total =
+    mean over images of pull * pull_b + push * push_b, dtag float32 [N,K,h,w] =
+    scale * d total / d tags or None).  dtag is written whole (a tensor given as dtag is
+    filled in place).  The definition is hkp_tag_loss's (include/hulkkp.h); nothing is
+    synchronised."""
+    from ._lib import lib
+    n, k, h, w = _tag_planes("tag_loss", low_all)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise HkpError("tag_loss: bad picture size %dx%d" % (H, W))
+    scale = _tag_weight("tag_loss", "scale", scale)
+    pull = _tag_weight("tag_loss", "pull", pull)
+    push = _tag_weight("tag_loss", "push", push)
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 4 or tuple(pts.shape[:2]) != (n, k) or pts.shape[3] != 3 \
+            or not 1 <= pts.shape[2] <= 16:
+        raise HkpError("tag_loss: pts must be [%d,%d,M,3] with 1 <= M <= 16, got %s"
+                       % (n, k, tuple(pts.shape) if isinstance(pts, torch.Tensor) else type(pts).__name__))
+    m = pts.shape[2]
+    if not isinstance(gid, torch.Tensor) or tuple(gid.shape) != (n, k, m):
+        raise HkpError("tag_loss: gid must be int32 [%d,%d,%d], got %s"
+                       % (n, k, m, tuple(gid.shape) if isinstance(gid, torch.Tensor) else type(gid).__name__))
+    if dtag is not None and (not want_grad or not isinstance(dtag, torch.Tensor) or tuple(dtag.shape) != (n, k, h, w)):
+        raise HkpError("tag_loss: dtag must be float32 [%d,%d,%d,%d] and goes with want_grad" % (n, k, h, w))
+    _need(low_all, torch.float32, "tag_loss.low_all", 4)
+    _need(pts, torch.float32, "tag_loss.pts", 4)
+    _need(gid, torch.int32, "tag_loss.gid", 3)
+    if dtag is not None:
+        _need(dtag, torch.float32, "tag_loss.dtag", 4)
+    for name, t in (("pts", pts), ("gid", gid), ("dtag", dtag)):
+        if t is not None and t.device != low_all.device:
+            raise HkpError("tag_loss: %s is on %s, low_all on %s" % (name, t.device, low_all.device))
+    out = torch.empty(3, device=low_all.device, dtype=torch.float64)
+    ws = torch.empty(lib().hkp_tag_loss_workspace(n) // 8, device=low_all.device, dtype=torch.float64)
+    if want_grad and dtag is None:
+        dtag = torch.empty((n, k, h, w), device=low_all.device, dtype=torch.float32)
+    call("hkp_tag_loss", n, k, m, h, w, H, W, _tags_ptr(low_all, k), 2 * k * h * w, _ptr(pts), _ptr(gid), scale, pull,
+         push, _ptr(out), _ptr(dtag), _ptr(ws), _stream())
+    return out, dtag
+
+
+def group_order(order, k):
+    """The class ids of peaks_group's `order` as a tuple of ints, validated as the kernel
+    validates them: 1 to K of them, each in 0..K-1, none twice."""
+    try:
+        od = tuple(order)
+    except TypeError:
+        raise HkpError("peaks_group: order must be a sequence of class ids, got %r" % (order,))
+    if not 1 <= len(od) <= k:
+        raise HkpError("peaks_group: order needs 1 to %d class ids, got %d" % (k, len(od)))
+    for c in od:
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < k:
+            raise HkpError("peaks_group: order %r: %r is no class of 0..%d" % (od, c, k - 1))
+    if len(set(od)) != len(od):
+        raise HkpError("peaks_group: order %r names a class twice" % (od,))
+    return od
+
+
+def peaks_group(peaks, counts, low_all, H, W, order, max_dist=1.0):
+    """Group the decoded peaks of heat_peaks (peaks float32 [N,K,P,3], counts int32 [N,K]) by
+    the tags of low_all [N,2K,h,w] (channels K..2K-1, read in place) → (group int32 [N,K,P],
+    tag float32 [N,K,P], ngroups int32 [N]).  tag: the tag map's bilinear value at every used
+    peak slot of every class (0 elsewhere).  group: per image the classes of `order` in turn
+    and their peaks best first, each joining the group (without a member of its class yet)
+    whose mean tag is nearest, if within max_dist, else opening a new one; -1 for unused
+    slots and classes not in order.  A greedy rule (hkp_peaks_group, include/hulkkp.h), not
+    a per-class Hungarian assignment.  One launch, nothing is synchronised."""
+    n, k, h, w = _tag_planes("peaks_group", low_all)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise HkpError("peaks_group: bad picture size %dx%d" % (H, W))
+    od = group_order(order, k)
+    md = ctypes.c_float(float(max_dist)).value
+    if not (md > 0.0 and md != float("inf")):
+        raise HkpError("peaks_group: max_dist must be finite and > 0, got %r" % (max_dist,))
+    if not isinstance(peaks, torch.Tensor) or peaks.dim() != 4 or tuple(peaks.shape[:2]) != (n, k) \
+            or peaks.shape[3] != 3 or not 1 <= peaks.shape[2] <= 16:
+        raise HkpError("peaks_group: peaks must be [%d,%d,P,3] with 1 <= P <= 16, got %s"
+                       % (n, k, tuple(peaks.shape) if isinstance(peaks, torch.Tensor) else type(peaks).__name__))
+    p = peaks.shape[2]
+    if not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (n, k):
+        raise HkpError("peaks_group: counts must be int32 [%d,%d]" % (n, k))
+    _need(low_all, torch.float32, "peaks_group.low_all", 4)
+    _need(peaks, torch.float32, "peaks_group.peaks", 4)
+    _need(counts, torch.int32, "peaks_group.counts", 2)
+    for name, t in (("peaks", peaks), ("counts", counts)):
+        if t.device != low_all.device:
+            raise HkpError("peaks_group: %s is on %s, low_all on %s" % (name, t.device, low_all.device))
+    group = torch.empty((n, k, p), device=low_all.device, dtype=torch.int32)
+    tag = torch.empty((n, k, p), device=low_all.device, dtype=torch.float32)
+    ngroups = torch.empty(n, device=low_all.device, dtype=torch.int32)
+    call("hkp_peaks_group", n, k, p, h, w, H, W, len(od), (ctypes.c_int32 * len(od))(*od), md, _ptr(peaks),
+         _ptr(counts), _tags_ptr(low_all, k), 2 * k * h * w, _ptr(tag), _ptr(group), _ptr(ngroups), _stream())
+    return group, tag, ngroups
+
+
 def head_bwd(dheat, heat, h, w):
     """dlow [N,K,h,w] = upsample-adjoint(dheat * (1-heat) * heat)."""
     _need(dheat, torch.float32, "head_bwd.dheat", 4)

@@ -92,6 +92,17 @@ def gather_peaks(peaks, counts, group=None):
     return tuple(_gather_ragged([peaks, counts], group))
 
 
+def gather_groups(groups, group=None):
+    """all_gather of each rank's peak groups (ops.peaks_group: int32 [b_r, K, P]) →
+    [sum b_r, K, P] in rank order, on every rank; shards may differ in size."""
+    if groups.dtype != torch.int32 or groups.dim() != 3:
+        raise ValueError("gather_groups: expected int32 [b, K, P], got %s %s" % (groups.dtype, tuple(groups.shape)))
+    n = dist.get_world_size(group) if dist.is_initialized() else 1
+    if n == 1:
+        return groups
+    return _gather_ragged([groups], group)[0]
+
+
 def gather_keypoints_fixed(yx, out=None, group=None):
     """gather_keypoints for equal shards (the bench's steady state): one
     all_gather_into_tensor, no size exchange; out: a [world*b, K, 2] int32 buffer

@@ -131,7 +131,7 @@ class Trainer:
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-4, loss="bce", sigma=8.0, distributed=False,
                  bucket_mb=32, optimizer="fused", sync_bn=False, group=None, force_buckets=False, absent="zero",
-                 max_grad_norm=None, ema_decay=None, loss_params=None):
+                 max_grad_norm=None, ema_decay=None, loss_params=None, tags=None):
         """loss: "bce", "mse" or "qfl" (ops.LOSS_KINDS); loss_params: the other keyword
         arguments of ops.heat_loss / ops.heat_loss_multi, e.g. {"beta": 2.0, "norm":
         "instances"} for the quality focal loss (point labels, uv or pts, only).  Under data
@@ -164,8 +164,21 @@ class Trainer:
         `group` (default: the world; the step then equals one step over the
         global batch), instead of per-rank BN (DDP semantics, the default).
         force_buckets: the DP gradient path (bucket copies, stream joins) at world
-        size 1, to time its overhead on one GPU."""
+        size 1, to time its overhead on one GPU.
+        tags: None, or a dict {"classes": (class indices), "weight": 1e-3, "pull": 1.0,
+        "push": 1.0} — associative-embedding tags (hkp.grouping): the head then runs over
+        the fc rows 0..2K-1 (2K <= 16), row K + c being the tag map of class c, and the
+        pull / push loss of ops.tag_loss on the stride-8 lattice, times weight (default
+        HigherHRNet's 1e-3), adds its gradient to dlow before the fc backward.  Tags need
+        pts labels; a step also takes gid int32 [B,K,M], the cable of every slot (None:
+        grouping.slot_groups — slot m of each listed class is cable m).  step() still
+        returns the heat loss; trainer.tag_loss is the step's device tensor (total, mean
+        pull, mean push), None without tags; no host synchronisation is added.  Under data
+        parallelism each rank divides by its own batch size, as the other losses do with
+        their divisors."""
         self.model = model
+        self.tags = self._tags_choice(tags, model.num_keypoints)
+        self.tag_loss = None
         self.group = group
         self.sync_bn = sync_bn
         # SyncBN gathers on their own communicator over the same ranks (RCCL orders
@@ -215,6 +228,28 @@ class Trainer:
         self.bucketer = GradBucketer(self.params, bucket_mb << 20, group=group) if (use_dp or force_buckets) \
             else None
 
+    @staticmethod
+    def _tags_choice(tags, k):
+        if tags is None:
+            return None
+        if not isinstance(tags, dict) or set(tags) - {"classes", "weight", "pull", "push"} or "classes" not in tags:
+            raise ValueError("tags must be a dict with classes and optionally weight, pull, push, got %r" % (tags,))
+        if 2 * k > 16:
+            raise ValueError("tags take the fc rows K..2K-1 of at most 16 head rows: K = %d is too many" % k)
+        classes = tuple(tags["classes"])
+        for c in classes:
+            if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < k:
+                raise ValueError("tags: classes are indices in 0..%d, got %r" % (k - 1, classes))
+        if not classes or len(set(classes)) != len(classes):
+            raise ValueError("tags: classes %r must name at least one class, none twice" % (classes,))
+        out = dict(classes=classes)
+        for name, dflt in (("weight", 1e-3), ("pull", 1.0), ("push", 1.0)):
+            try:
+                out[name] = ops._tag_weight("Trainer(tags)", name, tags.get(name, dflt))
+            except ops.HkpError as e:
+                raise ValueError(str(e))
+        return out
+
     def _plane_weights(self, weights, device):
         """class_weights[None, :] * weights as the kernel's [B,K] (either may be missing)."""
         if self._class_weights is not None and (self.class_weights is None or self.class_weights.device != device):
@@ -223,10 +258,11 @@ class Trainer:
             return None if self.class_weights is None else self.class_weights[None, :]
         return weights if self.class_weights is None else self.class_weights[None, :] * weights
 
-    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None):
+    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None):
         """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
         flag: the multi-instance target, absent planes per Trainer(absent=...)).
         weights: float32 [B,K] per-image plane weights (point labels only; see __init__).
+        gid: int32 [B,K,M], Trainer(tags=...) only: the group of every slot of pts.
         global_batch (SyncBN): the job's batch size — the same on every rank, x
         being this rank's hkp.parallel.shard_range share of it; lets the empty-shard
         guard run without a host collective (parallel.ShardCheck)."""
@@ -240,8 +276,15 @@ class Trainer:
                 raise ops.HkpError("Trainer: class_weights, topk and weights need pts or uv labels alone; a dense "
                                    "target is not supported")
             ops._planes_choice("Trainer", weights, self.topk)
+        self.tag_loss = None
+        if self.tags is None:
+            if gid is not None:
+                raise ops.HkpError("Trainer: gid goes with Trainer(tags=...)")
+        elif pts is None or uv is not None or target is not None:      # checked before the forward
+            raise ops.HkpError("Trainer: tags need pts labels alone; uv and a dense target carry no groups")
         trace = net.Trace(self.policy)
-        hm, _, _ = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace)
+        kw = {} if self.tags is None else {"tags": True}           # tags off: the call as it always was
+        hm, _, low = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace, **kw)
         if planes:
             w = self._plane_weights(weights, hm.device)
             if w is not None:
@@ -259,7 +302,16 @@ class Trainer:
             loss, dheat = ops.heat_loss(hm, target, uv, self.sigma, self.loss_kind, want_grad=True,
                                         **self.loss_params)
         grads = net.Grads(on_ready=self.bucketer.ready if self.bucketer else None)
-        net.keypoints_backward(m.resnet.net, trace, dheat, grads)
+        if self.tags is None:
+            net.keypoints_backward(m.resnet.net, trace, dheat, grads)
+        else:
+            tg = self.tags
+            if gid is None:
+                from .grouping import slot_groups
+                gid = slot_groups(pts.shape[0], pts.shape[1], pts.shape[2], tg["classes"], pts.device)
+            self.tag_loss, dtag = ops.tag_loss(low, pts, gid, hm.shape[2], hm.shape[3], tg["weight"], tg["pull"],
+                                               tg["push"])
+            net.keypoints_backward(m.resnet.net, trace, dheat, grads, dtag=dtag)
         if self.bucketer is not None:
             self.bucketer.finish()
         else:
@@ -267,8 +319,8 @@ class Trainer:
                 p.grad = grads[p]
         return loss
 
-    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None):
-        loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights)
+    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None):
+        loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid)
         self.opt.step()
         return loss
 

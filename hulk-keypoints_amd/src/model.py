@@ -97,6 +97,28 @@ class KeypointsGauss(nn.Module):
         return ops.heat_peaks(low, H, W, max_peaks=max_peaks, radius=radius, threshold=threshold)
 
     @torch.no_grad()
+    def predict_groups(self, x, classes, max_peaks=4, radius=1, threshold=0.0, max_dist=1.0, policy=None):
+        """Which peaks belong to one cable (associative-embedding tags, not in the
+        reference; a model trained with Trainer(tags=...)): (peaks float32
+        [B,K,max_peaks,3], counts int32 [B,K], group int32 [B,K,max_peaks], tag float32
+        [B,K,max_peaks]).  One forward over the fc rows 0..2K-1 (2K <= 16), then
+        ops.heat_peaks on a contiguous copy of the heat channels — peaks and counts are
+        predict_peaks' — then ops.peaks_group: the peaks of `classes` (class indices, taken
+        in that order, each class best peak first) grouped greedily by the tag map's value
+        at the peak, within max_dist of a group's mean tag; -1 for unused slots and other
+        classes.  tta= is not offered: tags are not merged across views (a view's tags are
+        its own arbitrary numbers)."""
+        from hkp import ops
+        k = self.num_keypoints
+        low_all = net.keypoints_forward(self.resnet.net, x, k, heat=False, argmax=False, pol=policy or self.policy,
+                                        upsample=False, tags=True)[2]
+        H, W = net.image_nchw_shape(x)[2:]
+        peaks, counts = ops.heat_peaks(low_all[:, :k].contiguous(), H, W, max_peaks=max_peaks, radius=radius,
+                                       threshold=threshold)
+        group, tag, _ = ops.peaks_group(peaks, counts, low_all, H, W, classes, max_dist=max_dist)
+        return peaks, counts, group, tag
+
+    @torch.no_grad()
     def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None, tta=None):
         """predict_peaks, then one launch that matches the peaks to `labels` ([B,K,M,3]
         (u, v, flag) or [B,K,2], in input pixels, on the device) and adds the outcome

@@ -47,6 +47,13 @@ class Prediction:
         keypoints().  kw: max_peaks, radius, threshold (KeypointsGauss.predict_peaks)."""
         return self.model.predict_peaks(self._batch(imgs), **kw)
 
+    def groups(self, imgs, classes, **kw):
+        """(peaks, counts, group int32 [B,K,P], tag float32 [B,K,P]): peaks() and, for the
+        class indices `classes`, the cable each peak belongs to, grouped on the GPU by the
+        model's tag maps (a model trained with tags).  kw: max_peaks, radius, threshold,
+        max_dist (KeypointsGauss.predict_groups); no tta."""
+        return self.model.predict_groups(self._batch(imgs), classes, **kw)
+
     def evaluate(self, imgs, labels, metrics, **kw):
         """peaks(), matched on the GPU to `labels` ([B,K,M,3] (u, v, flag) or [B,K,2]) and
         added into `metrics` (hkp.metrics.KeypointMetrics); kw as for peaks().  Returns

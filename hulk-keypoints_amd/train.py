@@ -48,6 +48,15 @@ that took part in the labels (plane_loss >= 0), reads the sums once per epoch an
 `train class loss: c0 ... cK-1` after `train loss:` and `test class loss: ...` after
 `test loss:`: the unweighted mean loss per pixel of each class (nan for a class that no
 image labelled).  Under data parallelism rank 0 prints its own shard's train values.
+With config.TAGS set (default None: nothing changes) — {"classes": ("cap", "tail"), "weight":
+1e-3, "pull": 1.0, "push": 1.0}, classes as indices or as names of config.SYNTH["classes"] —
+the train loop steps an hkp.train.Trainer built with tags=: the head also computes one tag map
+per class (fc rows K..2K-1), the pull / push loss of hkp_tag_loss trains the tags of one cable
+together and those of different cables apart (slot m of every listed class is cable m), and
+fit() prints `train tag loss: total pull push` after `train loss:`, summed on the GPU and read
+once per epoch.  The labels must be instances [B,K,M,3] (INSTANCES or SYNTH); the optimizer is
+the Trainer's FusedAdam (lr 1e-4, weight decay 1e-4, with MAX_GRAD_NORM / EMA_DECAY); the test
+loop is unchanged.  TAGS does not go with CLASS_LOSS.
 """
 import contextlib
 import os
@@ -60,7 +69,7 @@ from torch.utils.data import DataLoader
 from config import *  # noqa: F401,F403
 from config import (ABSENT, BACKBONE, CLASS_LOSS, DOMAIN_RANDOMIZATION, DR_SEED, EMA_DECAY, EVAL, GA_PARAMS, GA_SEED,
                     GAUSS_SIGMA, GEOMETRIC_AUGMENTATION, IMG_HEIGHT, IMG_WIDTH, INSTANCES, LOSS, LOSS_PARAMS,
-                    MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, SYNTH, batch_size, epochs)
+                    MAX_GRAD_NORM, NUM_KEYPOINTS, RESIZE, RESIZE_PARAMS, SYNTH, TAGS, batch_size, epochs)
 from hkp import autograd as hkp_autograd
 from hkp import net, ops
 from hkp.train import GradBucketer, broadcast_state
@@ -73,6 +82,7 @@ keypoints = None
 _bucketer = None
 _class_weights = {}     # device -> LOSS_PARAMS["class_weights"] as a float32 tensor, built once
 _class_acc = None       # CLASS_LOSS: float64 [2,K] on the device, per class the sum of plane_loss and the planes
+_trainer = None         # TAGS: the hkp.train.Trainer that steps the train loop
 
 
 def _rank0():
@@ -196,8 +206,47 @@ def _ema_weights():
     return contextlib.nullcontext(), False
 
 
+def _tags_config():
+    """config.TAGS as Trainer's tags= : class names go through config.SYNTH["classes"]."""
+    tags = dict(TAGS)
+    names = tuple(SYNTH["classes"]) if SYNTH is not None and "classes" in SYNTH else ()
+    classes = []
+    for c in tags.get("classes", ()):
+        if isinstance(c, str):
+            if c not in names:
+                raise ValueError("config.TAGS: class %r is not in config.SYNTH['classes'] %r" % (c, names))
+            c = names.index(c)
+        classes.append(c)
+    tags["classes"] = tuple(classes)
+    return tags
+
+
+def _tags_trainer(model):
+    """The Trainer of the train loop under config.TAGS (built once per model); its optimizer
+    becomes this module's."""
+    global _trainer, optimizer
+    if _trainer is None or _trainer.model is not model:
+        from hkp.train import Trainer
+        if CLASS_LOSS:
+            raise ValueError("config.TAGS does not go with CLASS_LOSS")
+        _trainer = Trainer(model, lr=1.0e-4, weight_decay=1.0e-4, loss=LOSS, sigma=GAUSS_SIGMA, absent=ABSENT,
+                           distributed=dist.is_initialized(), max_grad_norm=MAX_GRAD_NORM, ema_decay=EMA_DECAY,
+                           loss_params=LOSS_PARAMS, tags=_tags_config())
+        optimizer = _trainer.opt
+    return _trainer
+
+
+def _tags_step(trainer, sample_batched):
+    img, gt = sample_batched
+    if not (gt.dim() == 4 and gt.shape[-1] == 3 and gt.is_floating_point()):
+        raise ops.HkpError("config.TAGS needs instance labels [B,K,M,3] (INSTANCES or SYNTH), got %s"
+                           % (tuple(gt.shape),))
+    return trainer.step(img.cuda(non_blocking=True), pts=gt.cuda().float().contiguous())
+
+
 def fit(train_data, test_data, model, epochs, checkpoint_path=""):
     metrics = peak_kw = None
+    trainer = _tags_trainer(model) if TAGS is not None else None
     if EVAL is not None:            # every rank walks the whole test set: no reduction needed
         from hkp.metrics import from_config
         metrics, peak_kw = from_config(EVAL, model.num_keypoints)
@@ -210,18 +259,26 @@ def fit(train_data, test_data, model, epochs, checkpoint_path=""):
             train_data.dataset.set_epoch(epoch)     # the geometric augmentation draws per (seed, epoch, index)
         train_loss = 0.0
         i_batch = 0
+        tag_acc, tag_steps = None, 0
         for i_batch, sample_batched in enumerate(train_data):
-            optimizer.zero_grad()
-            loss = forward(sample_batched, model)
-            loss.backward()
-            _reduce_grads(model)
-            optimizer.step()
+            if trainer is not None:
+                loss = _tags_step(trainer, sample_batched)
+                tag_acc = trainer.tag_loss if tag_acc is None else tag_acc + trainer.tag_loss
+                tag_steps += 1
+            else:
+                optimizer.zero_grad()
+                loss = forward(sample_batched, model)
+                loss.backward()
+                _reduce_grads(model)
+                optimizer.step()
             train_loss += loss.item()
             if _rank0():
                 print("[%d, %5d] loss: %.3f" % (epoch + 1, i_batch + 1, loss.item()), end="")
                 print("\r", end="")
         if _rank0():
             print("train loss:", train_loss / max(i_batch, 1))   # reference divides by i_batch (train.py:40)
+            if tag_acc is not None:
+                print("train tag loss:", *[v / tag_steps for v in tag_acc.tolist()])
         _class_loss_line("train")
         test_loss = 0.0
         i_batch = 0
@@ -292,13 +349,15 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
                             num_workers=workers)
     test_data = DataLoader(test_dataset, batch_size=batch_size, shuffle=True, num_workers=workers)
     keypoints = KeypointsGauss(NUM_KEYPOINTS, img_height=IMG_HEIGHT, img_width=IMG_WIDTH, backbone=BACKBONE).cuda()
-    if MAX_GRAD_NORM is None and EMA_DECAY is None:
+    if TAGS is not None:                # the Trainer steps the train loop with its own FusedAdam
+        _tags_trainer(keypoints)
+    elif MAX_GRAD_NORM is None and EMA_DECAY is None:
         optimizer = torch.optim.Adam(keypoints.parameters(), lr=1.0e-4, weight_decay=1.0e-4)   # train.py:79
     else:                               # the same step with clipping and / or a weight EMA in its one pass
         from hkp.optim import FusedAdam
         optimizer = FusedAdam(keypoints.parameters(), lr=1.0e-4, weight_decay=1.0e-4, max_grad_norm=MAX_GRAD_NORM,
                               ema_decay=EMA_DECAY)
-    if world > 1:
+    if world > 1 and TAGS is None:
         setup_data_parallel(keypoints)
     fit(train_data, test_data, keypoints, epochs=epochs, checkpoint_path=save_dir)
     if dist.is_initialized():

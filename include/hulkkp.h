@@ -1191,6 +1191,81 @@ int hkp_logits_merge(int32_t n, int32_t k, int32_t h, int32_t w, int32_t views, 
                      const float* packed, const void* table, const int32_t* perm,
                      float* out, hkp_stream_t stream);
 
+/* ============================ associative-embedding tags: loss and grouping ==== */
+/* Which cap belongs to which tail (Newell et al., 2017; the grouping of
+ * HigherHRNet): one scalar tag map per keypoint class on the stride-8 lattice,
+ * trained so that the tags of one instance agree and those of different instances
+ * differ, and a decode that groups the peaks of hkp_heat_peaks by tag
+ * (csrc/tags.hip; tests/_tags_ref.py restates all of it in numpy).  Neither entry
+ * has a counterpart in the reference.
+ *
+ *  tag map      the tag map of class c is row k + c of the scoring conv, so tags need
+ *               2k <= 16 rows of the head: the low-res tensor with tags is
+ *               low_all [n][2k][h][w] fp32, heat logits in channels 0..k-1, tags in
+ *               channels k..2k-1.
+ *  in place     `tags` points at channel k of image 0 and batch_stride is the distance
+ *               in ELEMENTS between two images (2k*h*w for low_all; >= k*h*w); tags
+ *               needs 4-byte alignment only.  No copy of the tag planes is made.
+ *  frame        the frame of hkp_heat_peaks: pixel (u, v) of the H x W picture lies at
+ *               x = (double)u * (w-1) / (W-1) (0 when W == 1 or w == 1), y likewise,
+ *               each clamped to the lattice (x > 0 ? x : 0, then x < w-1 ? x : w-1: a
+ *               NaN goes to 0); x0 = min(floor(x), w-2) (0 when w == 1), fx = x - x0,
+ *               x1 = min(x0 + 1, w-1), and the same along y.
+ *  sample       the fp64 bilinear value of the fp32 map, without fused multiply-add:
+ *               top = (1-fx)*t[y0][x0] + fx*t[y0][x1], bot likewise on row y1,
+ *               t = (1-fy)*top + fy*bot.
+ *
+ * hkp_tag_loss: pts [n][k][m][3] (u, v, flag) as hkp_heat_loss_multi takes them and
+ * gid int32 [n][k][m], the group (cable) of each slot.  A slot takes part when its
+ * flag > 0 and 0 <= gid < 32; the (u, v) of any other slot are never read.  Per
+ * image, with t_i the samples of the participating points, G distinct groups, n_g
+ * members and mu_g their mean:
+ *    pull_b = (1/G) sum_g (1/n_g) sum_{i in g} (t_i - mu_g)^2
+ *    push_b = (1/(G(G-1))) sum_{g != g'} exp(-(mu_g - mu_g')^2 / 2),  0 for G < 2
+ * and an image without a group adds 0.  out[3] (fp64) = (total, mean pull, mean
+ * push) with total = (1/n) sum_b (pull_w*pull_b + push_w*push_b): the divisor is the
+ * constant n.  dtag [n][k][h][w] fp32 (NULL: no gradient) is WRITTEN WHOLE, +0 where
+ * no point reaches, and needs no memset: dtag = (float)(scale * d total / d map),
+ * formed in fp64 from the closed form
+ *    d pull_b / d t_i  = 2 (t_i - mu_g) / (G n_g)
+ *    d push_b / d mu_g = -(2/(G(G-1))) sum_{g' != g} (mu_g - mu_g') exp(-(mu_g - mu_g')^2 / 2)
+ *    d mu_g / d t_i    = 1 / n_g
+ * each point's gradient spread to its four taps by the bilinear weights.  A gather:
+ * every node sums, in slot order and tap order 00, 01, 10, 11, the taps that fall
+ * on it — no atomics, so the same input gives the same bits.  scale (the loss
+ * weight), pull_w and push_w travel as floats and must be finite and >= 0.
+ * workspace: hkp_tag_loss_workspace(n) bytes (the per-image pull and push).
+ * Limits: n >= 1, 1 <= k <= 8, 1 <= m <= 16, 1 <= h, w <= 32767, H, W >= 1;
+ * anything else is HKP_ERR_BAD_ARG and nothing is launched or written. */
+int64_t hkp_tag_loss_workspace(int32_t n);
+int hkp_tag_loss(int32_t n, int32_t k, int32_t m, int32_t h, int32_t w, int32_t H, int32_t W,
+                 const float* tags, int64_t batch_stride, const float* pts, const int32_t* gid,
+                 float scale, float pull_w, float push_w, double* out, float* dtag, void* workspace,
+                 hkp_stream_t stream);
+
+/* hkp_peaks_group: peaks [n][k][p][3] (x, y, score) and counts [n][k] of
+ * hkp_heat_peaks, the tag planes as above, and order_host, q distinct class ids
+ * (host memory, passed to the kernel by value), 1 <= q <= k.  Written whole:
+ *    tag     [n][k][p] fp32   the sample (rounded once to fp32) at every peak slot
+ *                             below min(max(count, 0), p), of every class; 0 elsewhere
+ *    group   [n][k][p] int32  the group of the peak; -1 for unused slots and for
+ *                             classes not in order
+ *    ngroups [n] int32
+ * Per image the classes are taken in `order` and the peaks in slot order (best
+ * first).  Each peak looks at the groups that do not yet hold a member of its
+ * class, with d_g = |t - mean_g| in fp64, mean_g the fp64 sum of the members' fp32
+ * tags divided by their count; the smallest d_g wins, equal values go to the lower
+ * group id; if that d_g <= (double)max_dist the peak joins the group, else it opens
+ * group ngroups++.  A NaN tag fails every comparison and opens a group.  A greedy
+ * rule, not HigherHRNet's per-class Hungarian assignment.  One wavefront per image,
+ * no atomics.  Limits: 1 <= k <= 8, 1 <= p <= 16, lattice as above, max_dist finite
+ * and > 0, order within 0..k-1 without repeats; anything else is HKP_ERR_BAD_ARG
+ * and nothing is launched or written. */
+int hkp_peaks_group(int32_t n, int32_t k, int32_t p, int32_t h, int32_t w, int32_t H, int32_t W, int32_t q,
+                    const int32_t* order_host, float max_dist, const float* peaks, const int32_t* counts,
+                    const float* tags, int64_t batch_stride, float* tag, int32_t* group, int32_t* ngroups,
+                    hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
