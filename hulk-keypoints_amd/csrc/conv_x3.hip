@@ -57,6 +57,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "x3_plan.h"
 
 namespace hkp {
 
@@ -377,8 +378,6 @@ __device__ __forceinline__ void x3_store(const X3Args& a, long off, float v, flo
 //   P = 3 (packed f16x3 split, chunks = hi32 | lo32):  hi*hi + hi*lo + lo*hi
 //   P = 2 / 4 (packed split): two of those three products (see the header)
 //   P = 1 (plain fp16, chunks = channels 0-31 | 32-63): two k-slices
-// operand layout of P: the packed hi|lo split (P 2, 3, 4) or plain fp16 (P 1)
-constexpr bool x3_packed(int P) { return P != 1; }
 // fp16 MFMAs per 128-B stage row pair
 constexpr int x3_nprod(int P) { return P == 3 ? 3 : 2; }
 
@@ -1681,7 +1680,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3_tail_kernel(X3Args a) {
 // other's MFMAs.  256 x 64 tile, 8 waves 4 x 2 (wave tile 64 x 32), 16x16x32
 // MFMAs; epilogue = the one-tile kernels' (BN tile partials from the
 // accumulators, LDS-staged 16-B row chunks), rows remapped to the patch pixels.
-constexpr int HALO_PH = 8, HALO_PW = 32, HALO_LW = HALO_PW + 2, HALO_NL = (HALO_PH + 2) * HALO_LW;   // 340 lines
+constexpr int HALO_LW = HALO_PW + 2, HALO_NL = (HALO_PH + 2) * HALO_LW;   // 340 lines (HALO_PH x HALO_PW patches: x3_plan.h)
 constexpr int HALO_GA = 6;                                   // halo DMA instructions per wave (48 x 8 lines >= 340)
 constexpr int HALO_ABYTES = 8 * HALO_GA * 8 * 128;           // 48 KiB: halo image (+ 44 dummy lines)
 constexpr int HALO_NSTB = 3, HALO_BSTAGE = 64 * 128;         // weight ring: 3 x 8 KiB
@@ -1696,11 +1695,6 @@ constexpr int HALO_LDS = HALO_ABYTES + HALO_NSTB * HALO_BSTAGE;
 // line hits 16 distinct 16-B bank slots (bit 0 of L picks the 128-B half, and the
 // group's two q values differ in bit 0 of the chunk).
 __device__ __forceinline__ int halo_swz(int L) { return L & 6; }
-
-static bool halo_shape(int stride, int r, int s, int pad, int dil, int ho, int wo, int k) {
-    return stride == 1 && r == 3 && s == 3 && pad == 1 && dil == 1 && ho % HALO_PH == 0 && wo % HALO_PW == 0 &&
-           k % 64 == 0;
-}
 
 // BNIN: the input is the producer's raw output and its BN + ReLU (+ the f16x3
 // split, P 3) is applied to each channel group's halo image in LDS after it
@@ -1973,7 +1967,7 @@ __global__ __launch_bounds__(512, 2) void conv_x3_halo_bnin_kernel(X3Args a) {
 // (row >> 1) & 7 chunk swizzle.  256 x 64 tile, 8 waves 4 x 2 (wave tile 64 x 32),
 // 16x16x32 MFMAs, 80 KiB: two blocks per CU, one's epilogue beside the other's
 // MFMAs; epilogue = the halo body's (BN tile partials, LDS-staged fp32 row chunks).
-constexpr int STEM_PH = 8, STEM_PW = 32, STEM_PR = 2 * STEM_PH + 5, STEM_PC = 2 * STEM_PW + 6;   // 21 x 70 pixels
+constexpr int STEM_PR = 2 * STEM_PH + 5, STEM_PC = 2 * STEM_PW + 6;   // 21 x 70 pixels (STEM_PH x STEM_PW patches: x3_plan.h)
 constexpr int STEM_PLANE = STEM_PR * STEM_PC * 8;                // bytes per plane (4 ch fp16 per pixel)
 constexpr int STEM_BBYTES = 7 * 64 * 128;                        // 7 filter rows x 64 weight lines
 constexpr int STEM_PCH = 2 * STEM_PLANE / 16;                    // patch 16-B chunks (1470)
@@ -1981,9 +1975,6 @@ constexpr int STEM_PGA = (STEM_PCH + 511) / 512;                 // patch DMA in
 constexpr int STEM_LDS = STEM_BBYTES + 8 * STEM_PGA * 1024;      // B, then the patch (+ dummy chunks): 80 KiB
 
 HKP_AB_KNOB(int, g_stem_pair, 0);                               // hkp_debug_stem_pair
-static bool stem_patch_shape(int ho, int wo, int k) {
-    return !g_stem_pair && ho % STEM_PH == 0 && wo % STEM_PW == 0 && k % 64 == 0;
-}
 
 // SRC: 0 the padded hi | lo planes of hkp_stem_pack_x3 (DMA), 1 the fp32 NCHW image,
 // 2 the uint8 NHWC (BGR) batch — for 1 / 2 the patch is built in LDS from the image
@@ -2171,7 +2162,7 @@ __global__ __launch_bounds__(512, 2) void conv_x3_stem_patch_kernel(X3Args a) {
 // half: no LDS merge), then the fp16 tile staged in the drained ring and written
 // as 16-B row chunks, optionally through the fused BN + residual + ReLU
 // (hkp_conv2d_fwd_f16_bn) — the 256x256 body's arithmetic, element for element.
-constexpr int DUO_BM = 256, DUO_BN = 128, DUO_ROW = 64, DUO_NST = 3;
+constexpr int DUO_BM = 256, DUO_ROW = 64, DUO_NST = 3;              // (DUO_BN = 128: x3_plan.h)
 // first-round arrivals per CU (key: XCC id x the HW_ID's SE / SH / CU bits): the
 // second block to arrive on a CU starts late, so the two blocks sharing it run
 // half a block apart (see conv_x3_duo_kernel); parity of a running count, never reset
@@ -3356,63 +3347,6 @@ __global__ __launch_bounds__(256) void wg_x3_reduce_kernel(long n4, int splits, 
     }
 }
 
-// wgrad_x3_halo_kernel's shapes: 3x3, stride 1, pad = dilation = 1, C and K
-// multiples of 64 up to 128 (the layers it was measured on), whole 4x16-pixel
-// patches, operands under 2 GiB (32-bit byte offsets); d->tile == -1 keeps the
-// tiled body (A/B, tests)
-static bool wg_halo_shape(const hkp_conv_desc* d, int ho, int wo) {
-    return d->tile != -1 && d->r == 3 && d->s == 3 && d->stride == 1 && d->pad == 1 && d->dilation == 1 &&
-           d->k % 64 == 0 && d->c % 64 == 0 && d->k <= 128 && d->c <= 128 && wo % 16 == 0 && ho % 4 == 0 &&
-           ho == d->h &&
-           wo == d->w && (long)d->n * d->h * d->w * d->c * 4 < (1L << 31) && (long)d->n * ho * wo * d->k * 4 < (1L << 31);
-}
-
-// ka = 0: the halo body (r_tiles = its 64-channel column tiles, mps = patches per split)
-static void wg_x3_plan(const hkp_conv_desc* d, long M, int wo, int* splits, int* mps, int* ka, int* r_tiles) {
-    if (wg_halo_shape(d, (int)(M / ((long)d->n * wo)), wo)) {
-        const long tiles = (long)(d->k / 64) * (d->c / 64), np = M / 64;   // 4x16-pixel patches
-        // one 130 KiB block per CU: one round of 256, or the caller's CU budget
-        long sp = std::max(1L, (d->tile > 0 ? d->tile : 256) / tiles);
-        sp = std::min(sp, np);
-        const long per = (np + sp - 1) / sp;
-        *ka = 0;
-        *r_tiles = d->c / 64;
-        *mps = (int)per;                                   // patches per split
-        *splits = (int)((np + per - 1) / per);
-        return;
-    }
-    // KA 256's 16-pixel stages advance each x slot with at most one row wrap
-    // (and 32-bit byte offsets into both operands)
-    const bool ka256 = d->k % 256 == 0 && wo >= 16 && (long)d->n * d->h * d->w * d->c * 4 < (1L << 32) &&
-                       M * d->k * 4 < (1L << 32);
-    *ka = ka256 ? 256 : d->k % 128 == 0 ? 128 : 64;
-    const long rsc = (long)d->r * d->s * d->c;
-    *r_tiles = (int)((rsc + 255) / 256);
-    const long tiles = (long)(d->k / *ka) * *r_tiles;
-    // One 512-thread block per CU at a time: pick the split count whose block
-    // count best fills whole rounds of 256 CUs (few rounds, few slabs to reduce),
-    // with at least 16 K-steps (512 pixels) per block.
-    const long max_sp = std::max(1L, (M + 511) / 512);
-    long sp = 1;
-    double best = -1.0;
-    for (long c = 1; c <= max_sp && d->tile <= 0; ++c) {
-        const long blocks = tiles * c;
-        const long rounds = (blocks + 255) / 256;
-        if (rounds > 4) break;
-        const double fill = (double)blocks / (256.0 * rounds);
-        const double score = fill - 0.03 * rounds;            // prefer fewer rounds / slabs at equal fill
-        if (score > best + 1e-9) {
-            best = score;
-            sp = c;
-        }
-    }
-    if (d->tile > 0) sp = std::max(1L, std::min<long>(max_sp, d->tile / tiles));   // the caller's CU budget
-    long m = (M + sp - 1) / sp;
-    m = (m + 31) / 32 * 32;
-    *splits = (int)((M + m - 1) / m);
-    *mps = (int)m;
-}
-
 
 // Stem operand: the image → zero-padded NHWC4 planes [2][N][Hp][Wp][4] (hi, then
 // lo = f16(x-hi)); padded pixel (hp, wp) = input (hp-3, wp-3).  U8: the image is
@@ -3471,11 +3405,6 @@ __global__ __launch_bounds__(256) void stem_weight_pack_x3_kernel(int C, const f
     if (threadIdx.x == 0) wscale[k] = 1.f / sc;
 }
 
-static bool stem_x3_shape(const hkp_conv_desc* d) {
-    return d && d->in_layout == HKP_LAYOUT_NCHW && d->c >= 1 && d->c <= 4 && d->r == 7 && d->s == 7 &&
-           d->stride == 2 && d->pad == 3 && d->dilation == 1 && d->k % 64 == 0;
-}
-
 // Compute units (one 512-thread conv block per CU at a time); cached per process.
 static int x3_cus() {
     static int n = [] {
@@ -3488,343 +3417,14 @@ static int x3_cus() {
     return n;
 }
 
-// stream-K: per-tile arrival counters in the first X3_SK_CNT_BYTES of the
-// workspace, then two fp32 slabs per block (a block splits at most its first
-// and its last tile): 2 * CUs * BN * 1 KiB (256 x BN floats per slab)
-constexpr long X3_SK_CNT_BYTES = 64 << 10;
-static long x3_sk_ws_bytes(int bn) { return X3_SK_CNT_BYTES + 2L * x3_cus() * bn * 1024; }
-
-// stream-K overhead per block in tile times: every block writes up to two
-// fp32 slabs and most reduce a tile from two (~0.4 MB per CU, all CUs at once),
-// plus a second pipeline fill — so it shrinks with the K depth nks of a tile.
-// Fitted to in-process A/Bs on the box (column-grouped stream-K vs one tile per
-// block): t4 nks 144 0.34, t3 / layer3 nks 72 0.46 / 0.48, t2 nks 36 0.63,
-// t1 / layer1 nks 18 1.18 / 1.46 tile-times: 0.2 + 19 / nks.
-static double sk_over(int nks) { return 0.2 + 19.0 / nks; }
-
-// Tile width (and data-parallel vs stream-K) for Cout = k over m_tiles 256-row
-// tiles: data-parallel costs ceil(blocks / CUs) rounds of one tile each,
-// stream-K blocks / CUs + the overhead above; minimise rounds x the measured
-// per-column tile cost (256x256: 0.9, 256x128: 1.0, 256x64: 1.25 — wider tiles
-// reuse each A line more).  E.g. C2 layer4 (600 m-tiles, Cout 512): 1200
-// 256x256 tiles = 4.69 rounds, data-parallel (5 rounds); training layer4 (150
-// m-tiles): 600 256x128 tiles stream-K (2.34 + 0.25 rounds) beats 3 rounds of
-// 256x128 (data-parallel's best).  Measured on C2 layer4: 256x256 1.70 ms vs
-// 256x128 1.82 ms; on C2 layer3 (Cout 256, 600 m-tiles) 256x256 loses to round
-// quantisation (0.53 vs 0.47 ms).  No stream-K with 256x256 tiles (the one-tile
-// 256x256 kernel sits at 255 VGPRs; the stream-K loop would spill).
-// Split-K tail (conv_x3_tail_kernel) for a one-tile grid of m_tiles x nt tiles:
-// the group count NG = tm*S of the tail grid (0: no tail) — each of the tm
-// m-tiles past the last full round in S equal K segments, one per group — and its
-// cost in tile times, 1/S + 0.08 (a segment's fill, slab hand-off and combine)
-// per round of segments.  C2 layer3 on 256x256 tiles (88 tail tiles): S = 2,
-// ~0.58 instead of 1; training t4: S = 5.  C2 layer4 (88 tail m-tiles x 2
-// columns) has no S >= 2 that beats one plain round.  (A fractional tail — every
-// CU's group a fraction of a tile, two segments per block — was built in round 5
-// and measured slower end to end: DESIGN "Fractional split-K tail".)
-// (Multi-round tails — S segments per tail m-tile past one round, one slab per
-// segment — measured slower in round 5: the B=8 shard's layer3 0.138 -> 0.164 ms
-// at S = 3, C2 layer3 0.384 -> 0.418 ms at S = 5; profiles/r05_multi_*.  The tail
-// on 256x128 grids of >= 2 rounds (C2 layer2) measured neutral: C2 1753.0 vs 1755.5
-// img/s, C4 / C3 unchanged; profiles/r05_tail128_*_v2.)
 HKP_AB_KNOB(int, g_x3_split_tail, 0);                 // hkp_debug_x3_split_tail
-static long x3_tail_groups(long m_tiles, int nt, int nks, double* cost = nullptr) {
-    const long G = x3_cus(), tiles = m_tiles * nt, tr = tiles % G;
-    const long tm = m_tiles - tiles / G * G / nt;
-    double best = 1.0;
-    long ng = 0;
-    if (tr > 0) {
-        for (int S = 2; S <= 8 && nks / S >= 4 && tm * S * nt <= G; ++S)
-            if (1.0 / S + 0.08 < best - 1e-9) {
-                best = 1.0 / S + 0.08;
-                ng = tm * S;
-            }
-    }
-    if (cost) *cost = tr > 0 ? best : 0.0;
-    return ng;
-}
-
-struct X3Plan {
-    int bn;
-    bool sk;
-};
-static X3Plan x3_plan(int k, long m_tiles, int nks, bool sk_ok, double over) {
-    const int G = x3_cus();
-    X3Plan best{64, false};
-    double best_cost = 1e300;
-    for (int bn : {256, 128, 64}) {
-        if (k % bn) continue;
-        const long tiles = m_tiles * (k / bn);
-        const double col = bn * (bn == 256 ? 0.9 : bn == 128 ? 1.0 : 1.25);
-        double tail = (tiles % G) ? 1.0 : 0.0;             // the last, partly filled round
-        if (bn == 256 && sk_ok) x3_tail_groups(m_tiles, k / bn, nks, &tail);
-        const double dp = ((double)(tiles / G) + tail) * col;
-        if (dp < best_cost - 1e-9) {
-            best_cost = dp;
-            best = {bn, false};
-        }
-        const int ng = G / (k / bn);       // column-grouped stream-K: groups of k/bn blocks
-        if (sk_ok && bn != 256 && ng > 0 && m_tiles % ng && tiles * 4 <= X3_SK_CNT_BYTES) {
-            const double skc = ((double)m_tiles / ng + over) * col;
-            if (skc < best_cost - 1e-9) {
-                best_cost = skc;
-                best = {bn, true};
-            }
-        }
-    }
-    return best;
-}
-
-// The kernel a launch runs (conv_x3_kernel<bn, STEM, pair, mfd, sk, P>):
-//   256x256                 16x16x32 body, 2-stage ring (C2 layer4 1.79 -> 1.62 ms
-//                           vs the 32x32x16 body: same cycles per FLOP at lower
-//                           power, so the chip holds a higher clock —
-//                           MI355X_MICROARCH.md DVFS item 7)
-//   256x128, >= 2 rounds    16x16x32 body, 3-stage ring (C2 layer3 +6 %, layer2 +5 %)
-//   256x128, one round      32x32x16 body (the 16x16 body's longer fill lost 8-11 %;
-//                           round 5: AUTO on packed f16x3 runs the 16x16 body here
-//                           and 256x64 pairs for >= 1 round — x3_choose)
-//   256x64                  16x16x32 body, two blocks per CU (layer1 0.223 -> 0.166 ms)
-//   stream-K 256x128 / 64   16x16x32 / 32x32x16 bodies (training t4 fwd +3-6 %, t3 +6 %)
-// hkp_conv_desc.tile (HKP_TILE_*) forces one of them — every body is reachable
-// for the parity tests; results agree to fp32 summation order.
-struct X3Choice {
-    int bn, mfd;
-    bool pair, sk;
-    bool halo = false;                 // conv_x3_halo_kernel<P>
-    bool a3 = false;                   // conv_x3_a3_kernel<P> (256x256, 3-stage A ring)
-    bool duo = false;                  // conv_x3_duo_kernel<1> (256x128, two 4-wave blocks per CU)
-    int bm = 256;                      // rows per tile (192 / 160: conv_x3_a3_192 / _160_kernel<P>)
-    bool mix = false;                  // conv_x3_a3_mix_kernel<P>: the regions of x3_mix_plan
-};
-
-// The regions of a mixed-height launch (conv_x3_a3_mix_kernel) over M rows and
-// n_tiles column tiles on G CUs: a, b, c rounds of 256-, 192- and 160-row tiles,
-// G / n_tiles m-tiles to a round, minimising the 16-row blocks a CU runs, 16 a +
-// 12 b + 10 c, subject to (G / n_tiles) (256 a + 192 b + 160 c) >= M.  The three
-// heights cost the same per row, so plans of equal cost tie: the one with the most
-// 256-row rounds, then the most 192-row rounds (the fewest blocks), is taken; four
-// 192-row or eight 160-row rounds are three / five 256-row ones, so b <= 3, c <= 7.
-// Regions in that order; every region but the last non-empty one holds its whole
-// rounds, the last only the tiles that the rows left need.
-struct X3Mix {
-    int cost = 0;                      // 16-row blocks per CU; 0: no plan
-    int rounds[3] = {0, 0, 0};
-    long mt[3] = {0, 0, 0};            // m-tiles per region
-    long m_base[3] = {0, 0, 0};        // first output row
-    long part_base[3] = {0, 0, 0};     // first BN partial tile (128- / 96- / 80-row tiles)
-    long part_tiles = 0;               // BN partial tiles in all
-};
-static constexpr int X3_MIX_BM[3] = {256, 192, 160};
-static X3Mix x3_mix_plan(long M, int n_tiles, int G) {
-    X3Mix p;
-    if (M <= 0 || n_tiles <= 0 || G / n_tiles <= 0) return p;
-    const long R = G / n_tiles, need = (M + R - 1) / R;        // m-tiles per round, rows a CU column must cover
-    const long a_hi = (need + 255) / 256, a_lo = std::max<long>(0, (need - 3 * 192 - 7 * 160) / 256);
-    long best = -1, ba = 0, bb = 0, bc = 0;
-    for (long a = a_hi; a >= a_lo; --a)
-        for (long b = 3; b >= 0; --b)
-            for (long c = 0; c <= 7; ++c) {
-                if (256 * a + 192 * b + 160 * c < need) continue;
-                const long cost = 16 * a + 12 * b + 10 * c;
-                if (best < 0 || cost < best) { best = cost; ba = a; bb = b; bc = c; }
-                break;                                         // more 160-row rounds only cost more
-            }
-    if (best < 0 || best > (1L << 30)) return p;
-    p.cost = (int)best;
-    p.rounds[0] = (int)ba; p.rounds[1] = (int)bb; p.rounds[2] = (int)bc;
-    const int last = bc ? 2 : bb ? 1 : 0;
-    long row = 0, pt = 0;
-    for (int r = 0; r < 3; ++r) {
-        const long bm = X3_MIX_BM[r], left = M - row;
-        p.m_base[r] = row;
-        p.part_base[r] = pt;
-        p.mt[r] = r == last ? (left + bm - 1) / bm : p.rounds[r] * R;
-        const long rows = r == last ? left : p.mt[r] * bm;
-        row += rows;
-        pt += (rows + bm / 2 - 1) / (bm / 2);
-    }
-    p.part_tiles = pt;
-    return p;
-}
-// a mix launch's shape rule: packed operands, 256-wide output tiles, more than one
-// round of 256-row tiles (x3_choose; the A3 operand-size limits are the entry points')
-static bool x3_mix_ok(int k, long m_tiles, int P) {
-    return x3_packed(P) && k % 256 == 0 && m_tiles * (k / 256) > x3_cus();
-}
-// halo: 0 the halo-tile body cannot take the shape, 1 it can (HKP_TILE_HALO
-// forces it), 2 it is also the default (64 input channels: measured faster;
-// at 128 channels it ties the ring bodies, which then stay)
-static X3Choice x3_choose_base(int k, long m_tiles, int nks, bool sk_ok, int policy, int halo);
-static X3Choice x3_choose(int k, long m_tiles, int nks, bool sk_ok, int policy, int halo, int P);
-// AUTO (= AUTO_A3): the planner's choice, its 256x256 one-tile grids on the A3
-// body (measured in-process on one box: C2 1721 -> 1741 img/s, C4 2616 -> 2657;
-// per conv -1...-4 % on the 1x1 and 3x3 shapes of C4, -1 % on C2's layer3/4;
-// HKP_TILE_256 / 256_TAIL keep the 2-stage body)
-// DUO (the plain-fp16 256x128 two-blocks-per-CU body) where forced and legal;
-// other operand layouts plan as AUTO
 HKP_AB_KNOB(int, g_x3_pair128, 1);                    // hkp_debug_x3_pair128
-static X3Choice x3_choose(int k, long m_tiles, int nks, bool sk_ok, int policy, int halo, int P) {
-    if (policy == HKP_TILE_DUO) {
-        if (P == 1 && k % DUO_BN == 0) {
-            X3Choice c{DUO_BN, 16, false, false};
-            c.duo = true;
-            return c;
-        }
-        policy = HKP_TILE_AUTO;
-    }
-    // the overlapped dgrad's A3 request (Policy.dgrad_overlap_tile) on a 64- or
-    // 128-channel output, which A3 cannot take: plan it as AUTO (the rules below)
-    if (policy == HKP_TILE_256_A3 && P == 3 && k % 256 != 0 && g_x3_pair128) policy = HKP_TILE_AUTO;
-    // 192-row A3 tiles: packed operands with 256-divisible outputs; AUTO otherwise
-    if (policy == HKP_TILE_192_A3 && (!x3_packed(P) || k % 256 != 0)) policy = HKP_TILE_AUTO;
-    if (policy == HKP_TILE_160_A3 && (!x3_packed(P) || k % 128 != 0)) policy = HKP_TILE_AUTO;
-    // mixed tile heights: the same operands over more than one round of tiles; AUTO otherwise
-    if (policy == HKP_TILE_MIX_A3 && !x3_mix_ok(k, m_tiles, P)) policy = HKP_TILE_AUTO;
-    if (policy != HKP_TILE_AUTO_A3 && policy != HKP_TILE_AUTO) return x3_choose_base(k, m_tiles, nks, sk_ok, policy, halo);
-    X3Choice c = x3_choose_base(k, m_tiles, nks, sk_ok, HKP_TILE_AUTO, halo);
-    if (c.bn == 256 && !c.sk && !c.halo && !c.pair) c.a3 = true;
-    // AUTO, plain fp16: the DUO body where it measured faster than the one-tile
-    // bodies (tools/conv_ab.py, in-process, profiles/r05_duo_*): K-depth 64 (one
-    // K-step: C4's layer1 1x1 expansions, 64 -> 256: -12 %, all fill and epilogue)
-    // and 128-wide outputs (layer2: -4...-10 % against the one-block 256x128 body);
-    // the long-K 256-wide shapes stay on A3 (DUO +10...+33 %: its half-line stream
-    // moves 1.5x the operand bytes per MAC).  AUTO_A3 keeps the round-4 planner.
-    if (policy == HKP_TILE_AUTO && P == 1 && !c.halo && k % DUO_BN == 0 && (nks == 1 || k == DUO_BN)) {
-        X3Choice d{DUO_BN, 16, false, false};
-        d.duo = true;
-        return d;
-    }
-    // AUTO, packed f16x3, one-tile grids: the 256x64 two-blocks-per-CU tiles (one
-    // block's fill and epilogue overlap the other's K loop) for short-K convs (the
-    // 1x1 downsamples, K-depth <= 256 channels: C2 128 -> 256 0.061 -> 0.052 ms;
-    // B=8 256 -> 512 0.061 -> 0.040 and 128 -> 256 0.021 -> 0.019) and where the
-    // cost table picks 256x128 tiles over at least a round of them (C2 layer2 3x3
-    // 0.140 -> 0.125 ms, its stride-2 conv1 0.086 -> 0.073, the 64 -> 128 downsample
-    // 0.033 -> 0.025); a one-round 256x128 grid on the 16x16x32 body (the B=8 shard's
-    // layer2 0.053 -> 0.040 ms: the 32x32x16 body's shorter fill no longer wins).
-    // Stream-K plans stay (B=8 layer3: 0.128 ms vs 0.138 on pairs), and so do grids
-    // of more than 3 rounds of 256x256 tiles, where the longer grid's steady state
-    // favours the larger tiles (C2 256 -> 512 downsample at 4.7 rounds: even; config
-    // C5 at 1280x960, 4.7-37 rounds: its 128-wide 3x3 1.05x, its 1x1s 1.04-1.27x
-    // slower on pairs).  tools/conv_ab.py, profiles/r05_l2_conv_ab*.log
-    if (policy == HKP_TILE_AUTO && P == 3 && !c.halo && !c.sk && g_x3_pair128) {
-        const bool small = (double)m_tiles * k <= 3.0 * 256 * x3_cus();
-        if (small && (nks <= 8 || (c.bn == 128 && m_tiles * (k / 128) >= x3_cus()))) return {64, 16, true, false};
-        if (c.bn == 128 && m_tiles * (k / 128) < x3_cus()) c.mfd = 16;
-    }
-    return c;
-}
-static X3Choice x3_choose_base(int k, long m_tiles, int nks, bool sk_ok, int policy, int halo) {
-    // the halo-tile body wherever the shape allows it, unless a tile body is forced
-    if ((halo >= 1 && policy == HKP_TILE_HALO) ||
-        (halo == 2 && (policy == HKP_TILE_AUTO || policy == HKP_TILE_256_TAIL || policy == HKP_TILE_256_A3 ||
-                       policy == HKP_TILE_192_A3 || policy == HKP_TILE_160_A3 || policy == HKP_TILE_MIX_A3))) {
-        X3Choice c{64, 16, true, false};
-        c.halo = true;
-        return c;
-    }
-    switch (policy) {
-        case HKP_TILE_256:
-            if (k % 256 == 0) return {256, 16, false, false};
-            break;
-        case HKP_TILE_128_MF16:
-            if (k % 128 == 0) return {128, 16, false, false};
-            break;
-        case HKP_TILE_128_MF32:
-            if (k % 128 == 0) return {128, 32, false, false};
-            break;
-        case HKP_TILE_64_PAIR:
-            return {64, 16, true, false};
-        case HKP_TILE_256_TAIL:            // 256x256, the partial last round as split-K segments
-            if (k % 256 == 0) return {256, 16, false, false};
-            break;
-        case HKP_TILE_256_A3:              // the same on the A3 body
-            if (k % 256 == 0) return {256, 16, false, false, false, true};
-            break;
-        case HKP_TILE_192_A3:              // 192x256 / 160x256 (160x128) tiles on the A3 body
-        case HKP_TILE_160_A3:              // (x3_choose checked the operands)
-            if (k % 256 == 0 || (policy == HKP_TILE_160_A3 && k % 128 == 0)) {
-                X3Choice c{k % 256 == 0 ? 256 : 128, 16, false, false, false, true};
-                c.bm = policy == HKP_TILE_192_A3 ? 192 : 160;
-                return c;
-            }
-            break;
-        case HKP_TILE_MIX_A3: {           // 256 / 192 / 160 x 256 regions in one launch (x3_choose checked)
-            X3Choice c{256, 16, false, false, false, true};
-            c.mix = true;
-            return c;
-        }
-        default:
-            break;
-    }
-    const bool sk = sk_ok && policy != HKP_TILE_NO_SK && policy != HKP_TILE_256_TAIL && policy != HKP_TILE_256_A3;
-    const X3Plan pl = x3_plan(k, m_tiles, nks, sk, policy == HKP_TILE_SK ? 0.0 : sk_over(nks));
-    if (pl.sk) return {pl.bn, pl.bn == 128 ? 16 : 32, false, true};
-    if (pl.bn == 256) return {256, 16, false, false};
-    if (pl.bn == 128) return {128, (double)m_tiles * (k / 128) >= 2.0 * x3_cus() ? 16 : 32, false, false};
-    return {64, 16, true, false};
-}
-
-static const X3Choice X3_STEM{64, 16, true, false};
-
-static int x3_kernel_name(const X3Choice& c, bool stem, int P, char* buf, int len) {
-    if (c.halo) return snprintf(buf, len, "conv_x3_halo_kernel<%d>", P);
-    if (c.duo) return snprintf(buf, len, "conv_x3_duo_kernel<%d>", P);
-    if (c.mix) return snprintf(buf, len, "conv_x3_a3_mix_kernel<%d>", P);
-    if (c.a3)
-        return snprintf(buf, len, c.bm == 192                  ? "conv_x3_a3_192_kernel<%d>"
-                                  : c.bm == 160 && c.bn == 128 ? "conv_x3_a3_160x128_kernel<%d>"
-                                  : c.bm == 160                ? "conv_x3_a3_160_kernel<%d>"
-                                                               : "conv_x3_a3_kernel<%d>", P);
-    return snprintf(buf, len, "conv_x3_kernel<%d, %s, %s, %d, %s, %d>", c.bn, stem ? "true" : "false",
-                    c.pair ? "true" : "false", c.mfd, c.sk ? "true" : "false", P);
-}
-
-// the A3 grid (conv_x3_a3_kernel<P>)
-template <int P>
-static void launch_a3(dim3 grid, hipStream_t st, const X3Args& a) {
-    hipLaunchKernelGGL(conv_x3_a3_kernel<P>, grid, dim3(512), 0, st, a);
-}
-
-template <int P>
-static void launch_x3_p(const X3Choice& c, dim3 grid, hipStream_t st, const X3Args& a) {
-    if (c.a3)
-        launch_a3<P>(grid, st, a);
-    else if (c.sk && c.bn == 128)
-        hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 16, true, P>), grid, dim3(512), 0, st, a);
-    else if (c.sk)
-        hipLaunchKernelGGL((conv_x3_kernel<64, false, false, 32, true, P>), grid, dim3(512), 0, st, a);
-    else if (c.bn == 256)
-        hipLaunchKernelGGL((conv_x3_kernel<256, false, false, 16, false, P>), grid, dim3(512), 0, st, a);
-    else if (c.bn == 128 && c.mfd == 16)
-        hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 16, false, P>), grid, dim3(512), 0, st, a);
-    else if (c.bn == 128)
-        hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 32, false, P>), grid, dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_x3_kernel<64, false, true, 16, false, P>), grid, dim3(512), 0, st, a);
-}
-
-// a.RS, a.cch (128-B lines per pixel), a.M ... set by the caller; P = operand
-// layout (3 packed f16x3 split, 1 plain fp16)
 HKP_AB_KNOB(unsigned long long*, g_x3_stamps, nullptr);   // hkp_debug_x3_stamps
 HKP_AB_KNOB(int, g_x3_stagger_ns, 0);                 // hkp_debug_x3_stagger
 HKP_AB_KNOB(int, g_x3_store, 0);                      // hkp_debug_x3_store
 HKP_AB_KNOB(int, g_duo_stagger_ns, -1);               // hkp_debug_duo_stagger
 HKP_AB_KNOB(int, g_x3_prio, 0);                       // hkp_debug_x3_prio
 HKP_AB_KNOB(int, g_x3_a_wrap, 0);                     // hkp_debug_x3_a_wrap
-
-// the halo-tile body takes this launch (shape, plain dense output, no fused
-// epilogue, 32-bit halo offsets)
-// lines: 128-B input lines per pixel (32 channels each for P 3, 64 for P 1)
-static int x3_halo_level(bool ok, int lines, int P) {
-    return !ok ? 0 : lines * (x3_packed(P) ? 32 : 64) <= 64 ? 2 : 1;
-}
-
-static bool x3_halo_ok(const X3Args& a, int k) {
-    return halo_shape(a.stride, a.R, a.S, a.pad, a.dil, a.Ho, a.Wo, k) && a.ost == 0 && a.ep_ss == nullptr &&
-           a.mt0 == 0 && a.plane == 0 && (long)a.N * a.H * a.W * a.cch * 64L + 64 < (1L << 32);
-}
 
 // run f with std::integral_constant<int, P> for a runtime operand layout P
 template <typename F>
@@ -3838,124 +3438,121 @@ static void x3_dispatch_p(int P, F&& f) {
     }
 }
 
-static void launch_x3(int k, long m_tiles, int policy, int P, hipStream_t st, X3Args& a, void* ws = nullptr,
-                      int64_t ws_bytes = 0) {
+// the planner's A/B knobs (x3_plan.h) as this build has them
+static X3Knobs x3_knobs() {
+    X3Knobs kn;
+    kn.pair128 = g_x3_pair128 != 0;
+    kn.split_tail = g_x3_split_tail != 0;
+    kn.stem_pair = g_stem_pair != 0;
+    kn.duo_stagger_ns = g_duo_stagger_ns;
+    return kn;
+}
+
+// the plan of a launch with the caller's stream-K workspace (ws, ws_bytes; nullable) on this device
+static X3LaunchPlan x3_plan_of(const X3Problem& p, int policy, const void* ws, int64_t ws_bytes) {
+    return x3_launch_plan(p, policy, ws ? ws_bytes : 0, x3_cus(), x3_knobs());
+}
+
+// the problem's geometry in the kernels' argument block
+static void x3_set_geometry(X3Args& a, const X3Problem& p) {
+    a.N = p.N; a.H = p.H; a.W = p.W; a.C = p.C; a.K = p.K; a.R = p.R; a.S = p.S;
+    a.stride = p.stride; a.pad = p.pad; a.dil = p.dil; a.Ho = p.Ho; a.Wo = p.Wo;
+    a.M = (int)p.M; a.cch = p.cch; a.RS = p.RS;
+    a.ost = p.ost; a.OH = p.OH; a.OW = p.OW; a.oy = p.oy; a.ox = p.ox;
+}
+
+// start the kernel of one planned launch on operand layout P (3 packed f16x3 split, 2 / 4
+// its two-product sets, 1 plain fp16).  The cases stand in the order in which the kernels
+// have always been instantiated, which is the order of the device code: keep it, append
+static void x3_start(const X3Launch& l, int P, hipStream_t st, const X3Args& a) {
+    const dim3 g((unsigned)l.blocks), b((unsigned)l.threads);
+    switch (l.kernel) {
+        case HKP_X3K_DUO:
+            hipLaunchKernelGGL(conv_x3_duo_kernel<1>, g, b, 0, st, a);
+            break;
+        case HKP_X3K_HALO_BNIN:
+            if (P == 3) hipLaunchKernelGGL(conv_x3_halo_bnin_kernel<3>, g, b, 0, st, a);
+            else hipLaunchKernelGGL(conv_x3_halo_bnin_kernel<1>, g, b, 0, st, a);
+            break;
+        case HKP_X3K_HALO:
+            x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL(conv_x3_halo_kernel<pc.value>, g, b, 0, st, a); });
+            break;
+        case HKP_X3K_A3_MIX:                   // mixed and shorter A3 tiles: packed operands only (x3_choose)
+            x3_dispatch_p(P, [&](auto pc) {
+                if constexpr (x3_packed(pc.value)) hipLaunchKernelGGL(conv_x3_a3_mix_kernel<pc.value>, g, b, 0, st, a);
+            });
+            break;
+        case HKP_X3K_A3_192:
+        case HKP_X3K_A3_160X128:
+        case HKP_X3K_A3_160:
+            x3_dispatch_p(P, [&](auto pc) {
+                if constexpr (x3_packed(pc.value)) {
+                    constexpr int Q = pc.value;
+                    if (l.kernel == HKP_X3K_A3_192) hipLaunchKernelGGL(conv_x3_a3_192_kernel<Q>, g, b, 0, st, a);
+                    else if (l.kernel == HKP_X3K_A3_160X128) hipLaunchKernelGGL(conv_x3_a3_160x128_kernel<Q>, g, b, 0, st, a);
+                    else hipLaunchKernelGGL(conv_x3_a3_160_kernel<Q>, g, b, 0, st, a);
+                }
+            });
+            break;
+        case HKP_X3K_A3:
+            x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL(conv_x3_a3_kernel<pc.value>, g, b, 0, st, a); });
+            break;
+        case HKP_X3K_SK_128:                   // conv_x3_kernel's stream-K and one-tile forms
+        case HKP_X3K_SK_64:
+        case HKP_X3K_TILE_256:
+        case HKP_X3K_TILE_128_MF16:
+        case HKP_X3K_TILE_128_MF32:
+        case HKP_X3K_PAIR_64:
+            x3_dispatch_p(P, [&](auto pc) {
+                constexpr int Q = pc.value;
+                if (l.kernel == HKP_X3K_SK_128)
+                    hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 16, true, Q>), g, b, 0, st, a);
+                else if (l.kernel == HKP_X3K_SK_64)
+                    hipLaunchKernelGGL((conv_x3_kernel<64, false, false, 32, true, Q>), g, b, 0, st, a);
+                else if (l.kernel == HKP_X3K_TILE_256)
+                    hipLaunchKernelGGL((conv_x3_kernel<256, false, false, 16, false, Q>), g, b, 0, st, a);
+                else if (l.kernel == HKP_X3K_TILE_128_MF16)
+                    hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 16, false, Q>), g, b, 0, st, a);
+                else if (l.kernel == HKP_X3K_TILE_128_MF32)
+                    hipLaunchKernelGGL((conv_x3_kernel<128, false, false, 32, false, Q>), g, b, 0, st, a);
+                else
+                    hipLaunchKernelGGL((conv_x3_kernel<64, false, true, 16, false, Q>), g, b, 0, st, a);
+            });
+            break;
+        case HKP_X3K_TAIL:
+            x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL((conv_x3_tail_kernel<256, pc.value>), g, b, 0, st, a); });
+            break;
+        default:
+            break;
+    }
+}
+
+// Run plan pl of problem p: a holds the caller's pointers and epilogue; the geometry is the
+// problem's, every launch's grid and tile arithmetic the plan's (x3_plan.h)
+static void launch_x3(const X3Problem& p, const X3LaunchPlan& pl, hipStream_t st, X3Args& a, void* ws) {
+    x3_set_geometry(a, p);
     a.stamps = g_x3_stamps;
     a.st_kind = g_x3_store;
     a.prio = g_x3_prio;
 #ifdef HKP_AB_KNOBS
     a.a_wrap = g_x3_a_wrap;
 #endif
-    a.stagger_ticks = g_x3_stagger_ns / 10;
-    a.stagger_blocks = x3_cus();
-    const bool sk_ok = ws && ws_bytes >= x3_sk_ws_bytes(256);
-    const int nks = a.RS * a.cch;
-    const X3Choice c = x3_choose(k, m_tiles, nks, sk_ok, policy, x3_halo_level(x3_halo_ok(a, k), a.cch, P), P);
-    a.n_tiles = k / c.bn;
-    a.nks = nks;
-    a.sk_units = 0;
-    if (c.duo) {
-        // first-round stagger of the second block on each CU: half a block's
-        // lifetime, ~(fill + epilogue + K loop) / 2 — hkp_debug_duo_stagger overrides
-        // (ns; 0 = off, < 0 = this estimate)
-        const long blocks = m_tiles * a.n_tiles;
-        const int ns = g_duo_stagger_ns < 0 ? 5500 + 450 * 2 * nks : g_duo_stagger_ns;
-        a.stagger_ticks = blocks > 2L * x3_cus() ? ns / 10 : 0;
-        a.stagger_blocks = 2 * x3_cus();
-        hipLaunchKernelGGL(conv_x3_duo_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-        return;
-    }
-    if (c.halo) {
-        const dim3 gh((unsigned)(m_tiles * a.n_tiles));
-        if (a.in_ss) {
-            if (P == 3) hipLaunchKernelGGL(conv_x3_halo_bnin_kernel<3>, gh, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL(conv_x3_halo_bnin_kernel<1>, gh, dim3(512), 0, st, a);
-        } else {
-            x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL(conv_x3_halo_kernel<pc.value>, gh, dim3(512), 0, st, a); });
+    for (int i = 0; i < pl.n_launches; ++i) {
+        const X3Launch& l = pl.launch[i];
+        if (l.blocks == 0) continue;       // a tail-only grid's full rounds
+        X3Args t = a;
+        t.n_tiles = l.n_tiles; t.nks = l.nks; t.sk_units = l.sk_units; t.sk_one = l.sk_one; t.mt0 = l.mt0;
+        t.main_blocks = l.main_blocks; t.tail_groups = l.tail_groups; t.tail_mt0 = l.tail_mt0; t.tail_units = l.tail_units;
+        t.mix_b1 = l.mix_b1; t.mix_b2 = l.mix_b2; t.mix_m1 = l.mix_m1; t.mix_m2 = l.mix_m2;
+        t.mix_p1 = l.mix_p1; t.mix_p2 = l.mix_p2;
+        t.stagger_blocks = l.stagger_blocks;
+        t.stagger_ticks = (l.stagger_ns < 0 ? g_x3_stagger_ns : l.stagger_ns) / 10;
+        if (l.uses_ws) {
+            t.sk_cnt = (unsigned*)ws;
+            t.sk_ws = (float*)((char*)ws + X3_SK_CNT_BYTES);
         }
-        return;
+        x3_start(l, p.P, st, t);
     }
-    if (c.mix) {                           // one tile per block in up to three regions; no tail, no workspace
-        const X3Mix mp = x3_mix_plan(a.M, a.n_tiles, x3_cus());
-        X3Args t = a;
-        t.mix_b1 = (int)(mp.mt[0] * a.n_tiles);
-        t.mix_b2 = (int)((mp.mt[0] + mp.mt[1]) * a.n_tiles);
-        t.mix_m1 = (int)mp.m_base[1]; t.mix_m2 = (int)mp.m_base[2];
-        t.mix_p1 = (int)mp.part_base[1]; t.mix_p2 = (int)mp.part_base[2];
-        const dim3 gx((unsigned)((mp.mt[0] + mp.mt[1] + mp.mt[2]) * a.n_tiles));
-        x3_dispatch_p(P, [&](auto pc) {
-            if constexpr (x3_packed(pc.value))
-                hipLaunchKernelGGL(conv_x3_a3_mix_kernel<pc.value>, gx, dim3(512), 0, st, t);
-        });
-        return;
-    }
-    if (c.bm != 256) {                     // one tile per block, no split-K tail
-        const long mt = ((long)a.M + c.bm - 1) / c.bm;
-        const dim3 gm((unsigned)(mt * a.n_tiles));
-        x3_dispatch_p(P, [&](auto pc) {
-            if constexpr (x3_packed(pc.value)) {
-                if (c.bm == 192) hipLaunchKernelGGL(conv_x3_a3_192_kernel<pc.value>, gm, dim3(512), 0, st, a);
-                else if (c.bn == 128) hipLaunchKernelGGL(conv_x3_a3_160x128_kernel<pc.value>, gm, dim3(512), 0, st, a);
-                else hipLaunchKernelGGL(conv_x3_a3_160_kernel<pc.value>, gm, dim3(512), 0, st, a);
-            }
-        });
-        return;
-    }
-    dim3 grid((unsigned)(m_tiles * a.n_tiles));
-    if (c.sk) {
-        a.sk_units = m_tiles * a.nks;
-        a.sk_cnt = (unsigned*)ws;
-        a.sk_ws = (float*)((char*)ws + X3_SK_CNT_BYTES);
-        // at least one unit per group: an empty group range inside a tile's group
-        // span would be counted as a segment that never arrives
-        const long ng = std::min<long>(x3_cus() / a.n_tiles, a.sk_units);
-        grid = dim3((unsigned)(ng * a.n_tiles));
-    }
-    // split-K tail for the 256x256 one-tile grid (auto, or forced by HKP_TILE_256_TAIL)
-    const long tiles = m_tiles * a.n_tiles;
-    const long G = x3_cus();
-    const long rm = tiles / G * G / a.n_tiles;              // m-tiles of the full rounds
-    const long tm = m_tiles - rm;
-    long NG = (!c.sk && c.bn == 256 && sk_ok &&
-               (policy == HKP_TILE_AUTO || policy == HKP_TILE_256_TAIL || policy == HKP_TILE_256_A3 ||
-                policy == HKP_TILE_AUTO_A3))
-                  ? x3_tail_groups(m_tiles, a.n_tiles, nks)
-                  : 0;
-    // one round, every group non-empty and inside one tile (NG = tm * S), one slab
-    // per block and the counters in the workspace
-    if (NG > 0 && !(tm > 0 && NG % tm == 0 && NG * a.n_tiles <= G && tm * nks >= NG &&
-                    NG * a.n_tiles * 256L * 1024 + X3_SK_CNT_BYTES <= ws_bytes && tm * a.n_tiles * 4 <= X3_SK_CNT_BYTES))
-        NG = 0;
-    const bool tail = NG > 0;
-    a.sk_one = tail;
-    // one launch: the full rounds, then the tail's segments
-    if (tail && c.a3 && !g_x3_split_tail) {
-        X3Args t = a;
-        t.main_blocks = (int)(rm * a.n_tiles);
-        t.tail_groups = (int)NG;
-        t.tail_mt0 = (int)rm;
-        t.tail_units = tm * nks;
-        t.sk_cnt = (unsigned*)ws;
-        t.sk_ws = (float*)((char*)ws + X3_SK_CNT_BYTES);
-        const dim3 g1((unsigned)((rm + NG) * a.n_tiles));
-        x3_dispatch_p(P, [&](auto pc) { launch_a3<pc.value>(g1, st, t); });
-        return;
-    }
-    if (tail) {
-        if (rm > 0) {
-            dim3 g0((unsigned)(rm * a.n_tiles));
-            x3_dispatch_p(P, [&](auto pc) { launch_x3_p<pc.value>(c, g0, st, a); });     // (A3 body, A/B only)
-        }
-        X3Args t = a;
-        t.mt0 = (int)rm;
-        t.sk_units = tm * nks;
-        t.sk_cnt = (unsigned*)ws;
-        t.sk_ws = (float*)((char*)ws + X3_SK_CNT_BYTES);
-        const dim3 gt((unsigned)(NG * a.n_tiles));
-        x3_dispatch_p(P, [&](auto pc) { hipLaunchKernelGGL((conv_x3_tail_kernel<256, pc.value>), gt, dim3(512), 0, st, t); });
-        return;
-    }
-    x3_dispatch_p(P, [&](auto pc) { launch_x3_p<pc.value>(c, grid, st, a); });
 }
 
 }  // namespace hkp
@@ -3981,14 +3578,7 @@ extern "C" int hkp_weight_pack_f16(int32_t k, int32_t rsc, const float* w, uint1
     return HKP_OK;
 }
 
-extern "C" int64_t hkp_conv_x3_sk_workspace_bytes(void) { return x3_sk_ws_bytes(256); }
-
-// the kernels address operands with 32-bit element offsets (see conv_x3_tile):
-// the input ([n][h][w][cstride] halves, plus a padded-out margin of up to 64
-// rows) and the weights ([k][rs][cstride]) must fit
-static bool x3_offsets_fit(long n, long h, long w, long cstride, long k, long rs) {
-    return (n * h * w + 64 * (w + 65)) * cstride < (1L << 32) && k * rs * cstride < (1L << 31);
-}
+extern "C" int64_t hkp_conv_x3_sk_workspace_bytes(void) { return x3_sk_ws_bytes(256, x3_cus()); }
 
 static int check_tile(const hkp_conv_desc* d, const char* who) {
     HKP_CHECK_ARG(d->tile >= HKP_TILE_AUTO && d->tile <= HKP_TILE_MIX_A3, "%s: unknown tile policy %d", who,
@@ -4019,26 +3609,23 @@ static int conv_fwd_x3_common(const hkp_conv_desc* d, const uint16_t* xs, const 
     X3Args a;
     a.xs = (const _Float16*)xs; a.ws = (const _Float16*)ws; a.wscale = wsc;
     a.y = y; a.y16 = (_Float16*)y16; a.part = part; a.amax = nullptr; a.add = nullptr; a.plane = 0;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.C = d->c; a.K = d->k; a.R = d->r; a.S = d->s;
-    a.stride = d->stride; a.pad = d->pad; a.dil = d->dilation; a.Ho = ho; a.Wo = wo;
-    a.M = (int)M; a.cch = d->c / cg; a.RS = d->r * d->s;
-    int policy = d->tile;
+    X3Problem p = x3_problem_fwd(d, ho, wo, P);
     if (ep) {
         a.ep_ss = ep->ep_ss; a.ep_res = ep->ep_res; a.ep_rss = ep->ep_rss; a.ep_relu = ep->ep_relu;
         a.in_ss = ep->in_ss;
+        p.out_bn = ep->ep_ss != nullptr;
+        p.in_bn = ep->in_ss != nullptr;
     }
-    if (a.in_ss) {
+    const X3LaunchPlan pl = x3_plan_of(p, d->tile, sk_ws, sk_bytes);
+    if (p.in_bn) {
         // the fused input BN runs where the unfused conv would run the halo-tile body,
         // so its output is the unfused path's, bit for bit
         HKP_CHECK_ARG(P == 3 || P == 1, "%s: fused input BN needs f16x3 or plain fp16", who);
-        const bool sk_ok = sk_ws && sk_bytes >= x3_sk_ws_bytes(256);
-        const X3Choice c = x3_choose(d->k, (M + 255) / 256, a.RS * a.cch, sk_ok, d->tile,
-                                     x3_halo_level(x3_halo_ok(a, d->k), a.cch, P), P);
-        HKP_CHECK_ARG(c.halo,
+        HKP_CHECK_ARG(pl.c.halo,
                       "%s: the fused input BN needs a launch on the halo-tile body (stride-1 3x3, pad = dil = 1, "
                       "Ho %% 8 == 0, Wo %% 32 == 0)", who);
     }
-    launch_x3(d->k, (M + 255) / 256, policy, P, as_stream(stream), a, sk_ws, sk_bytes);
+    launch_x3(p, pl, as_stream(stream), a, sk_ws);
     HKP_LAUNCH_CHECK(who);
     return HKP_OK;
 }
@@ -4145,31 +3732,13 @@ extern "C" int hkp_conv2d_bwd_data_x3(const hkp_conv_desc* d, const uint16_t* dy
     X3Args a;
     a.xs = (const _Float16*)dy_split; a.ws = (const _Float16*)wf_split; a.wscale = wf_inv_scale;
     a.y = dx; a.part = nullptr; a.amax = (const unsigned*)dy_amax_bits; a.add = add; a.plane = 0;
-    a.N = d->n; a.H = ho; a.W = wo; a.C = d->k; a.K = d->c; a.R = d->r; a.S = d->s;
-    a.stride = 1; a.pad = padp; a.dil = d->dilation; a.Ho = d->h; a.Wo = d->w;
-    a.M = (int)M; a.cch = d->k / 32; a.RS = d->r * d->s;
-    launch_x3(d->c, (M + 255) / 256, d->tile, 3, as_stream(stream), a, sk_workspace, sk_ws_bytes);
+    const X3Problem p = x3_problem_dgrad(d, ho, wo);
+    launch_x3(p, x3_plan_of(p, d->tile, sk_workspace, sk_ws_bytes), as_stream(stream), a, sk_workspace);
     HKP_LAUNCH_CHECK("hkp_conv2d_bwd_data_x3");
     return HKP_OK;
 }
 
-// Strided dgrad as stride-1 convs, one per output phase (py, px) of dx: dx pixel
-// (2a+py, 2b+px) receives the taps r = r_max - 2r' (r ≡ py + pad mod 2) at dy row
-// a + o_min + r', o_min = (py + pad - r_max) / 2 (likewise for columns); a phase
-// no tap reaches (e.g. odd pixels of a 1x1 stride-2 conv) is dx = add (or 0).
-static int phase_taps(int R, int pad, int stride, int ph, int* r_max, int* o_min) {
-    int rm = -1;
-    for (int r = R - 1; r >= 0; --r)
-        if ((((ph + pad - r) % stride) + stride) % stride == 0) {
-            rm = r;
-            break;
-        }
-    if (rm < 0) return 0;
-    *r_max = rm;
-    *o_min = (ph + pad - rm) / stride;
-    return rm / stride + 1;
-}
-
+// (strided dgrad as stride-1 convs, one per output phase: phase_taps, x3_plan.h)
 __global__ __launch_bounds__(256) void phase_fill_kernel(long total, int C4, int Ha, int Wa, int OH, int OW, int ost,
                                                         int oy, int ox, const f32x4* __restrict__ add,
                                                         f32x4* __restrict__ dx) {
@@ -4212,10 +3781,9 @@ extern "C" int hkp_conv2d_bwd_data_x3_strided(const hkp_conv_desc* d, const uint
             const int ph = py * 2 + px;
             const int Ha = (d->h - py + 1) / 2, Wa = (d->w - px + 1) / 2;
             if (Ha <= 0 || Wa <= 0) continue;
-            int rmx = 0, omy = 0, smx = 0, omx = 0;
-            const int R2 = phase_taps(d->r, d->pad, 2, py, &rmx, &omy);
-            const int S2 = phase_taps(d->s, d->pad, 2, px, &smx, &omx);
-            if (R2 == 0 || S2 == 0) {
+            X3Problem p;
+            int col_pad = 0;
+            if (!x3_problem_dgrad_phase(d, ho, wo, py, px, &p, &col_pad)) {
                 HKP_CHECK_ARG(phase_split[ph] == nullptr, "hkp_conv2d_bwd_data_x3_strided: phase %d has no taps", ph);
                 const long total = (long)d->n * Ha * Wa * (d->c / 4);
                 long g = (total + 255) / 256;
@@ -4230,14 +3798,10 @@ extern "C" int hkp_conv2d_bwd_data_x3_strided(const hkp_conv_desc* d, const uint
             X3Args a;
             a.xs = (const _Float16*)dy_split; a.ws = (const _Float16*)phase_split[ph]; a.wscale = phase_inv_scale[ph];
             a.y = dx; a.part = nullptr; a.amax = (const unsigned*)dy_amax_bits; a.add = add; a.plane = 0;
-            a.N = d->n; a.H = ho; a.W = wo; a.C = d->k; a.K = d->c; a.R = R2; a.S = S2;
-            a.stride = 1; a.pad = -omy; a.dil = 1; a.Ho = Ha; a.Wo = Wa;
-            a.M = d->n * Ha * Wa; a.cch = d->k / 32; a.RS = R2 * S2;
-            a.ost = 2; a.OH = d->h; a.OW = d->w; a.oy = py; a.ox = px;
             // the column offset: the kernel applies one pad to both axes
-            HKP_CHECK_ARG(omx == omy, "hkp_conv2d_bwd_data_x3_strided: row/column phase offsets differ (%d, %d)",
-                          omy, omx);
-            launch_x3(d->c, ((long)a.M + 255) / 256, d->tile, 3, st, a, sk_workspace, sk_ws_bytes);
+            HKP_CHECK_ARG(col_pad == p.pad, "hkp_conv2d_bwd_data_x3_strided: row/column phase offsets differ (%d, %d)",
+                          -p.pad, -col_pad);
+            launch_x3(p, x3_plan_of(p, d->tile, sk_workspace, sk_ws_bytes), st, a, sk_workspace);
             HKP_LAUNCH_CHECK("hkp_conv2d_bwd_data_x3_strided");
         }
     return HKP_OK;
@@ -4361,9 +3925,7 @@ extern "C" int hkp_conv2d_fwd_stem_x3(const hkp_conv_desc* d, const uint16_t* x_
     a.stamps = g_x3_stamps;
     a.st_kind = g_x3_store;
     const long m_tiles = (M + 255) / 256;
-    if (stem_patch_shape(ho, wo, d->k) && d->tile != HKP_TILE_64_PAIR) {
-        // the patch body (patch-divisible outputs: 480x640 and 960x1280 images);
-        // HKP_TILE_64_PAIR keeps the one-tile stem (A/B, parity tests)
+    if (stem_patch_ok(d, ho, wo, x3_knobs())) {
         hipLaunchKernelGGL(conv_x3_stem_patch_kernel<0>, dim3(m_tiles * a.n_tiles), dim3(512), 0, as_stream(stream), a);
         HKP_LAUNCH_CHECK("hkp_conv2d_fwd_stem_x3");
         return HKP_OK;
@@ -4381,7 +3943,7 @@ extern "C" int hkp_conv2d_fwd_stem_x3(const hkp_conv_desc* d, const uint16_t* x_
 extern "C" int32_t hkp_stem_x3_image_ok(const hkp_conv_desc* d) {
     int ho, wo;
     if (!stem_x3_shape(d) || hkp_conv_out_hw(d, &ho, &wo) != HKP_OK) return 0;
-    return stem_patch_shape(ho, wo, d->k) && d->tile != HKP_TILE_64_PAIR && (long)d->n * ho * wo < (1L << 31) ? 1 : 0;
+    return stem_patch_ok(d, ho, wo, x3_knobs()) && (long)d->n * ho * wo < (1L << 31) ? 1 : 0;
 }
 
 extern "C" int hkp_conv2d_fwd_stem_x3_image(const hkp_conv_desc* d, const void* image, int32_t image_u8,
@@ -4408,60 +3970,78 @@ extern "C" int hkp_conv2d_fwd_stem_x3_image(const hkp_conv_desc* d, const void* 
     return HKP_OK;
 }
 
-// rows per BN statistic tile of a packed forward conv (see hulkkp.h)
-extern "C" int32_t hkp_conv_x3_stat_tile_rows(const hkp_conv_desc* d, int32_t op) {
-    HKP_CHECK_ARG(d, "hkp_conv_x3_stat_tile_rows: null descriptor");
-    if (op != HKP_KOP_FWD_X3 && op != HKP_KOP_FWD_X3_W16 && op != HKP_KOP_FWD_X3_X16 && op != HKP_KOP_FWD_F16) return 128;
-    int32_t seg[6];
-    const int n = hkp_conv_x3_stat_layout(d, op, seg);
-    return n < 0 ? n : seg[0];         // a mix launch's list has several (hkp_conv_x3_stat_layout)
-}
-
-// the body a forward launch with this descriptor runs (the launcher's x3_choose), and M
-static int x3_fwd_choice(const hkp_conv_desc* d, int32_t op, bool sk, X3Choice* c, long* m_out, const char* who) {
+// The plan of the launch that entry point `op` (HKP_KOP_*: the f16x3 / fp16 forwards, the
+// stride-1 dgrad, the stem) runs for d on cus CUs, with or without a stream-K workspace;
+// *P its operand layout.  The one reading of a descriptor that the name, the BN-partial
+// layout and the plan queries share with the launcher (x3_problem_* and x3_launch_plan).
+static int x3_op_plan(const hkp_conv_desc* d, int32_t op, bool sk, int cus, X3LaunchPlan* pl, X3Problem* p,
+                      const char* who) {
     int ho, wo;
     int rc = hkp_conv_out_hw(d, &ho, &wo);
     if (rc) return rc;
     rc = check_tile(d, who);
     if (rc) return rc;
-    HKP_CHECK_ARG(op == HKP_KOP_FWD_X3 || op == HKP_KOP_FWD_X3_W16 || op == HKP_KOP_FWD_X3_X16 || op == HKP_KOP_FWD_F16,
-                  "%s: not a forward conv op %d", who, op);
-    const int P = op == HKP_KOP_FWD_X3 ? 3 : op == HKP_KOP_FWD_X3_W16 ? 2 : op == HKP_KOP_FWD_X3_X16 ? 4 : 1;
-    const long m = (long)d->n * ho * wo;
-    const int cg = x3_packed(P) ? 32 : 64;
-    const int nks = d->r * d->s * (d->c / cg);
-    const bool halo = halo_shape(d->stride, d->r, d->s, d->pad, d->dilation, ho, wo, d->k) &&
-                      (long)d->n * d->h * d->w * (d->c / cg * 64L) + 64 < (1L << 32);
-    *c = x3_choose(d->k, (m + 255) / 256, nks, sk, d->tile, x3_halo_level(halo, d->c / cg, P), P);
-    *m_out = m;
+    switch (op) {
+        case HKP_KOP_FWD_X3: *p = x3_problem_fwd(d, ho, wo, 3); break;
+        case HKP_KOP_FWD_X3_W16: *p = x3_problem_fwd(d, ho, wo, 2); break;
+        case HKP_KOP_FWD_X3_X16: *p = x3_problem_fwd(d, ho, wo, 4); break;
+        case HKP_KOP_FWD_F16: *p = x3_problem_fwd(d, ho, wo, 1); break;
+        case HKP_KOP_FWD_F16_BN:
+            *p = x3_problem_fwd(d, ho, wo, 1);
+            p->out_bn = true;
+            break;
+        case HKP_KOP_DGRAD_X3: *p = x3_problem_dgrad(d, ho, wo); break;
+        case HKP_KOP_STEM_X3:
+        case HKP_KOP_STEM_X3_IMAGE:
+        case HKP_KOP_STEM_X3_IMAGE_U8: {   // one launch of 256x64 tiles over the 7 filter rows, 128-row partials
+            HKP_CHECK_ARG(op == HKP_KOP_STEM_X3 || hkp_stem_x3_image_ok(d),
+                          "%s: the image stem needs the patch body's shape", who);
+            *p = x3_problem_fwd(d, ho, wo, 3);
+            X3Launch& l = pl->launch[0];
+            l.kernel = op == HKP_KOP_STEM_X3_IMAGE      ? HKP_X3K_STEM_PATCH_IMAGE
+                       : op == HKP_KOP_STEM_X3_IMAGE_U8 ? HKP_X3K_STEM_PATCH_U8
+                       : stem_patch_ok(d, ho, wo, x3_knobs()) ? HKP_X3K_STEM_PATCH
+                                                        : HKP_X3K_STEM_PAIR;
+            l.n_tiles = d->k / 64;
+            l.nks = 7;
+            l.blocks = p->m_tiles() * l.n_tiles;
+            pl->n_launches = 1;
+            pl->n_seg = 1;
+            pl->seg[0] = 128;
+            pl->seg[1] = (int)((p->M + 127) / 128);
+            return HKP_OK;
+        }
+        default:
+            HKP_CHECK_ARG(false, "%s: not an f16x3 / fp16 conv op %d", who, op);
+    }
+    *pl = x3_launch_plan(*p, d->tile, sk ? x3_sk_ws_bytes(256, cus) : 0, cus, x3_knobs());
     return HKP_OK;
 }
 
-// the segments of a forward conv's BN partial list (see hulkkp.h)
+static bool x3_stat_op(int32_t op) {
+    return op == HKP_KOP_FWD_X3 || op == HKP_KOP_FWD_X3_W16 || op == HKP_KOP_FWD_X3_X16 || op == HKP_KOP_FWD_F16;
+}
+
+// rows per BN statistic tile of a packed forward conv (see hulkkp.h)
+extern "C" int32_t hkp_conv_x3_stat_tile_rows(const hkp_conv_desc* d, int32_t op) {
+    HKP_CHECK_ARG(d, "hkp_conv_x3_stat_tile_rows: null descriptor");
+    if (!x3_stat_op(op)) return 128;
+    int32_t seg[6];
+    const int n = hkp_conv_x3_stat_layout(d, op, seg);
+    return n < 0 ? n : seg[0];         // a mix launch's list has several (hkp_conv_x3_stat_layout)
+}
+
+// the segments of a forward conv's BN partial list (see hulkkp.h): the plan's, for a call
+// that passes the stream-K workspace
 extern "C" int32_t hkp_conv_x3_stat_layout(const hkp_conv_desc* d, int32_t op, int32_t* segments) {
     HKP_CHECK_ARG(d && segments, "hkp_conv_x3_stat_layout: null argument");
-    X3Choice c{64, 16, true, false};
-    long m = 0;
-    const int rc = x3_fwd_choice(d, op, true, &c, &m, "hkp_conv_x3_stat_layout");
+    HKP_CHECK_ARG(x3_stat_op(op), "hkp_conv_x3_stat_layout: not a forward conv op %d", op);
+    X3LaunchPlan pl;
+    X3Problem p;
+    const int rc = x3_op_plan(d, op, true, x3_cus(), &pl, &p, "hkp_conv_x3_stat_layout");
     if (rc) return rc < 0 ? rc : -rc;
-    for (int i = 0; i < 6; ++i) segments[i] = 0;
-    if (c.mix) {
-        const X3Mix mp = x3_mix_plan(m, d->k / 256, x3_cus());
-        int n = 0;
-        for (int r = 0; r < 3; ++r) {
-            if (mp.mt[r] == 0) continue;
-            const long end = r == 2 ? mp.part_tiles : mp.part_base[r + 1];
-            segments[2 * n] = X3_MIX_BM[r] / 2;
-            segments[2 * n + 1] = (int32_t)(end - mp.part_base[r]);
-            ++n;
-        }
-        return n;
-    }
-    // the halo-tile and DUO bodies write 128-row partials whatever the policy asked for
-    const int rows = c.halo || c.duo || c.bm == 256 ? 128 : c.bm / 2;
-    segments[0] = rows;
-    segments[1] = (int32_t)((m + rows - 1) / rows);
-    return 1;
+    for (int i = 0; i < 6; ++i) segments[i] = pl.seg[i];
+    return pl.n_seg;
 }
 
 // the regions of a mixed-height launch (see hulkkp.h): pure host arithmetic
@@ -4481,60 +4061,74 @@ extern "C" int32_t hkp_conv_x3_mix_plan(int64_t m, int32_t n_tiles, int32_t cus,
     return n;
 }
 
-// the kernel symbol a launch with this descriptor runs (see hulkkp.h)
+// the wgrad kernel of d and its grid
+static int wg_kernel_name(const hkp_conv_desc* d, int ho, int wo, char* buf, int len, long* blocks) {
+    int sp, mps, ka, rt;
+    wg_x3_plan(d, (long)d->n * ho * wo, wo, &sp, &mps, &ka, &rt);
+    *blocks = (long)(d->k / (ka ? ka : 64)) * rt * sp;
+    if (ka == 0) return snprintf(buf, len, "wgrad_x3_halo_kernel");
+    return snprintf(buf, len, "wgrad_x3_kernel<%d>", ka);
+}
+
+// the launches of a conv entry point (see hulkkp.h): pure host arithmetic
+extern "C" int32_t hkp_conv_x3_launch_plan(const hkp_conv_desc* d, int32_t op, int32_t stream_k_ok, int32_t cus,
+                                           int32_t launch_index, char* name_buf, int32_t len, int64_t* out) {
+    HKP_CHECK_ARG(d && name_buf && len > 0 && out && cus >= 0, "hkp_conv_x3_launch_plan: bad args");
+    if (cus == 0) cus = x3_cus();
+    for (int i = 0; i < HKP_X3_LAUNCH_PLAN_LEN; ++i) out[i] = 0;
+    out[29] = cus;
+    if (op == HKP_KOP_WGRAD_X3) {          // a wgrad's d->tile is its CU budget: its own planner (wg_x3_plan)
+        int ho, wo;
+        const int rc = hkp_conv_out_hw(d, &ho, &wo);
+        if (rc) return rc;
+        HKP_CHECK_ARG(d->k % 64 == 0, "hkp_conv_x3_launch_plan: wgrad needs Cout%%64==0");
+        HKP_CHECK_ARG(launch_index == 0, "hkp_conv_x3_launch_plan: launch %d of 1", launch_index);
+        long blocks = 0;
+        wg_kernel_name(d, ho, wo, name_buf, len, &blocks);
+        out[0] = -1;
+        out[1] = blocks;
+        out[2] = 512;
+        out[30] = (long)d->n * ho * wo;
+        return 1;
+    }
+    X3LaunchPlan pl;
+    X3Problem p;
+    const int rc = x3_op_plan(d, op, stream_k_ok != 0, cus, &pl, &p, "hkp_conv_x3_launch_plan");
+    if (rc) return rc;
+    HKP_CHECK_ARG(launch_index >= 0 && launch_index < std::max(1, pl.n_launches),
+                  "hkp_conv_x3_launch_plan: launch %d of %d", launch_index, pl.n_launches);
+    const X3Launch& l = pl.launch[launch_index];
+    x3_kernel_name(l.kernel, p.P, name_buf, len);
+    const int64_t v[22] = {l.kernel, l.blocks, l.threads, l.n_tiles, l.nks, l.sk_units, l.sk_one, l.mt0,
+                           l.main_blocks, l.tail_groups, l.tail_mt0, l.tail_units, l.mix_b1, l.mix_b2, l.mix_m1,
+                           l.mix_m2, l.mix_p1, l.mix_p2, l.stagger_blocks, l.stagger_ns, l.uses_ws, l.ws_bytes};
+    for (int i = 0; i < 22; ++i) out[i] = v[i];
+    for (int i = 0; i < 6; ++i) out[22 + i] = pl.seg[i];
+    out[28] = pl.n_seg;
+    out[30] = p.M;
+    out[31] = p.m_tiles();
+    out[32] = pl.c.bn;
+    out[33] = pl.c.bm;
+    return pl.n_launches;
+}
+
+// the kernel symbol a launch with this descriptor runs (see hulkkp.h): the plan's first launch
 extern "C" int32_t hkp_conv_kernel_name(const hkp_conv_desc* d, int32_t op, int32_t stream_k_ok, char* buf,
                                         int32_t len) {
     HKP_CHECK_ARG(d && buf && len > 0, "hkp_conv_kernel_name: bad args");
-    int ho, wo;
-    int rc = hkp_conv_out_hw(d, &ho, &wo);
-    if (rc) return rc;
-    if (op != HKP_KOP_WGRAD_X3) {          // a wgrad's d->tile is its CU budget
-        rc = check_tile(d, "hkp_conv_kernel_name");
+    if (op == HKP_KOP_WGRAD_X3) {
+        int ho, wo;
+        const int rc = hkp_conv_out_hw(d, &ho, &wo);
         if (rc) return rc;
+        HKP_CHECK_ARG(d->k % 64 == 0, "hkp_conv_kernel_name: wgrad needs Cout%%64==0");
+        long blocks = 0;
+        return wg_kernel_name(d, ho, wo, buf, len, &blocks);
     }
-    const bool sk = stream_k_ok != 0;
-    switch (op) {
-        case HKP_KOP_FWD_X3:
-        case HKP_KOP_FWD_X3_W16:
-        case HKP_KOP_FWD_X3_X16:
-        case HKP_KOP_FWD_F16: {
-            const int P = op == HKP_KOP_FWD_X3 ? 3 : op == HKP_KOP_FWD_X3_W16 ? 2 : op == HKP_KOP_FWD_X3_X16 ? 4 : 1;
-            const long m = (long)d->n * ho * wo;
-            const int cg = x3_packed(P) ? 32 : 64;
-            const int nks = d->r * d->s * (d->c / cg);
-            const bool halo = halo_shape(d->stride, d->r, d->s, d->pad, d->dilation, ho, wo, d->k) &&
-                              (long)d->n * d->h * d->w * (d->c / cg * 64L) + 64 < (1L << 32);
-            return x3_kernel_name(x3_choose(d->k, (m + 255) / 256, nks, sk, d->tile, x3_halo_level(halo, d->c / cg, P), P),
-                                  false, P, buf, len);
-        }
-        case HKP_KOP_DGRAD_X3: {
-            const long m = (long)d->n * d->h * d->w;
-            const int nks = d->r * d->s * (d->k / 32);
-            const int padp = d->dilation * (d->r - 1) - d->pad;
-            const bool halo = halo_shape(d->stride, d->r, d->s, padp, d->dilation, d->h, d->w, d->c) &&
-                              (long)d->n * ho * wo * (d->k / 32 * 64L) + 64 < (1L << 32);
-            return x3_kernel_name(x3_choose(d->c, (m + 255) / 256, nks, sk, d->tile, x3_halo_level(halo, d->k / 32, 3), 3),
-                                  false, 3, buf, len);
-        }
-        case HKP_KOP_STEM_X3:
-            if (stem_patch_shape(ho, wo, d->k) && d->tile != HKP_TILE_64_PAIR)
-                return snprintf(buf, len, "conv_x3_stem_patch_kernel<0>");
-            return x3_kernel_name(X3_STEM, true, 3, buf, len);
-        case HKP_KOP_STEM_X3_IMAGE:
-        case HKP_KOP_STEM_X3_IMAGE_U8:
-            HKP_CHECK_ARG(hkp_stem_x3_image_ok(d), "hkp_conv_kernel_name: the image stem needs the patch body's shape");
-            return snprintf(buf, len, "conv_x3_stem_patch_kernel<%d>", op == HKP_KOP_STEM_X3_IMAGE ? 1 : 2);
-        case HKP_KOP_WGRAD_X3: {
-            HKP_CHECK_ARG(d->k % 64 == 0, "hkp_conv_kernel_name: wgrad needs Cout%%64==0");
-            int sp, mps, ka, rt;
-            wg_x3_plan(d, (long)d->n * ho * wo, wo, &sp, &mps, &ka, &rt);
-            if (ka == 0) return snprintf(buf, len, "wgrad_x3_halo_kernel");
-            return snprintf(buf, len, "wgrad_x3_kernel<%d>", ka);
-        }
-        default:
-            HKP_CHECK_ARG(false, "hkp_conv_kernel_name: unknown op %d", op);
-    }
-    return HKP_ERR_BAD_ARG;
+    X3LaunchPlan pl;
+    X3Problem p;
+    const int rc = x3_op_plan(d, op, stream_k_ok != 0, x3_cus(), &pl, &p, "hkp_conv_kernel_name");
+    if (rc) return rc;
+    return x3_kernel_name(pl.launch[0].kernel, p.P, buf, len);
 }
 
 #ifdef HKP_AB_KNOBS   // the A/B instruments (tools/ab_lib build only; include/hulkkp_ab.h)

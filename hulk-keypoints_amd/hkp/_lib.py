@@ -40,9 +40,19 @@ class ConvDesc(ctypes.Structure):
  HKP_TILE_DUO, HKP_TILE_RESERVED_14, HKP_TILE_192_A3, HKP_TILE_160_A3, HKP_TILE_MIX_A3) = range(18)
 # hkp_conv_kernel_name ops
 HKP_KOP_FWD_X3, HKP_KOP_DGRAD_X3, HKP_KOP_FWD_F16, HKP_KOP_STEM_X3, HKP_KOP_WGRAD_X3, HKP_KOP_FWD_X3_W16, \
-    HKP_KOP_FWD_X3_X16, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8 = range(9)
+    HKP_KOP_FWD_X3_X16, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8, HKP_KOP_FWD_F16_BN = range(10)
 HKP_X3_W16, HKP_X3_ALL, HKP_X3_X16 = 2, 3, 4          # hkp_conv2d_fwd_x3_products product sets
 HKP_MIX_PLAN_LEN = 14                                 # hkp_conv_x3_mix_plan's out[]
+HKP_X3_LAUNCH_PLAN_LEN = 34                           # hkp_conv_x3_launch_plan's out[]
+# its kernel ids (out[0])
+HKP_X3K_TILE_256, HKP_X3K_TILE_128_MF16, HKP_X3K_TILE_128_MF32, HKP_X3K_PAIR_64, HKP_X3K_SK_128, HKP_X3K_SK_64, \
+    HKP_X3K_A3, HKP_X3K_A3_192, HKP_X3K_A3_160, HKP_X3K_A3_160X128, HKP_X3K_A3_MIX, HKP_X3K_TAIL, HKP_X3K_HALO, \
+    HKP_X3K_HALO_BNIN, HKP_X3K_DUO, HKP_X3K_STEM_PAIR, HKP_X3K_STEM_PATCH, HKP_X3K_STEM_PATCH_IMAGE, \
+    HKP_X3K_STEM_PATCH_U8, HKP_X3K_COUNT = range(20)
+# the per-launch values of out[], in order
+X3_LAUNCH_FIELDS = ("kernel", "blocks", "threads", "n_tiles", "nks", "sk_units", "sk_one", "mt0", "main_blocks",
+                    "tail_groups", "tail_mt0", "tail_units", "mix_b1", "mix_b2", "mix_m1", "mix_m2", "mix_p1", "mix_p2",
+                    "stagger_blocks", "stagger_ns", "uses_ws", "ws_bytes")
 
 
 class PackJob(ctypes.Structure):
@@ -159,6 +169,7 @@ SIGNATURES = {
     "hkp_conv_x3_stat_tile_rows": (_I32, [_CD, _I32]),
     "hkp_conv_x3_stat_layout": (_I32, [_CD, _I32, ctypes.POINTER(_I32)]),
     "hkp_conv_x3_mix_plan": (_I32, [_I64, _I32, _I32, ctypes.POINTER(_I32)]),
+    "hkp_conv_x3_launch_plan": (_I32, [_CD, _I32, _I32, _I32, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64)]),
     "hkp_conv2d_fwd": (ctypes.c_int, [_CD, _P, _P, _P, _P, _P]),
     "hkp_bn_finalize": (ctypes.c_int, [_I32, _I64, _I64, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hkp_bn_finalize_workspace_bytes": (_I64, [_I32, _I64]),

@@ -8,9 +8,10 @@ import ctypes
 
 import torch
 
-from ._lib import (HKP_KOP_DGRAD_X3, HKP_KOP_FWD_F16, HKP_KOP_FWD_X3, HKP_KOP_FWD_X3_W16, HKP_KOP_FWD_X3_X16,
-                   HKP_KOP_STEM_X3, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8, HKP_KOP_WGRAD_X3, HKP_X3_ALL,
-                   HKP_LAYOUT_NCHW, HKP_LAYOUT_NHWC, HKP_TILE_160_A3, HKP_TILE_192_A3, HKP_TILE_MIX_A3, ConvDesc, HkpError, call)
+from ._lib import (HKP_KOP_DGRAD_X3, HKP_KOP_FWD_F16, HKP_KOP_FWD_F16_BN, HKP_KOP_FWD_X3, HKP_KOP_FWD_X3_W16,
+                   HKP_KOP_FWD_X3_X16, HKP_KOP_STEM_X3, HKP_KOP_STEM_X3_IMAGE, HKP_KOP_STEM_X3_IMAGE_U8,
+                   HKP_KOP_WGRAD_X3, HKP_X3_ALL, HKP_LAYOUT_NCHW, HKP_LAYOUT_NHWC, HKP_TILE_160_A3, HKP_TILE_192_A3,
+                   HKP_TILE_MIX_A3, ConvDesc, HkpError, call)
 
 CONV_TILE_ROWS = 128  # BM of conv_fwd.hip (rows per BN statistic tile)
 
@@ -128,14 +129,38 @@ class PackedWeight(tuple):
 
 
 def kernel_name(d, op, sk=True):
-    """The kernel symbol a launch with ConvDesc d runs (hkp_conv_kernel_name: the
-    launcher's own tile choice, so the name cannot drift from what runs)."""
+    """The kernel symbol a launch with ConvDesc d runs (hkp_conv_kernel_name: the first
+    launch of the plan the launcher itself reads, so the name cannot drift from what runs)."""
     from ._lib import lib
     buf = ctypes.create_string_buffer(128)
     n = lib().hkp_conv_kernel_name(ctypes.byref(d), op, int(bool(sk)), buf, 128)
     if n < 0:
         raise HkpError("hkp_conv_kernel_name failed: %s" % lib().hkp_last_error().decode(errors="replace"))
     return buf.value.decode()
+
+
+def launch_plan(d, op, sk=True, cus=0):
+    """The launches entry point op runs for ConvDesc d on cus CUs (0: this device's;
+    hkp_conv_x3_launch_plan, the plan the launcher itself reads): a list of dicts, one per
+    launch — name, the _lib.X3_LAUNCH_FIELDS values, and the plan-wide segments
+    ((rows, tiles), ...), cus, m, m_tiles, bn, bm.  Empty where the entry point would
+    reject the shape."""
+    from ._lib import HKP_X3_LAUNCH_PLAN_LEN, X3_LAUNCH_FIELDS, lib
+    out, i, n = [], 0, 1
+    while i < n:
+        buf = ctypes.create_string_buffer(128)
+        v = (ctypes.c_int64 * HKP_X3_LAUNCH_PLAN_LEN)()
+        n = lib().hkp_conv_x3_launch_plan(ctypes.byref(d), op, int(bool(sk)), cus, i, buf, 128, v)
+        if n < 0:
+            raise HkpError("hkp_conv_x3_launch_plan failed: %s" % lib().hkp_last_error().decode(errors="replace"))
+        if n == 0:
+            break
+        one = dict(zip(X3_LAUNCH_FIELDS, v), name=buf.value.decode(),
+                   segments=tuple((v[22 + 2 * j], v[23 + 2 * j]) for j in range(v[28])),
+                   cus=v[29], m=v[30], m_tiles=v[31], bn=v[32], bm=v[33])
+        out.append(one)
+        i += 1
+    return out
 
 
 def weight_pack_x3(w):
@@ -396,7 +421,7 @@ def conv2d_fwd_f16_bn(x16, wp, ss, res=None, res_ss=None, relu=True, stride=1, p
     if _observer is None:
         launch()
     else:
-        _observer(kernel_name(d, HKP_KOP_FWD_F16, sk), 2.0 * n * ho * wo * k * r * s_ * c,
+        _observer(kernel_name(d, HKP_KOP_FWD_F16_BN, sk), 2.0 * n * ho * wo * k * r * s_ * c,
                   2.0 * (x16.numel() + ws.numel() + out.numel() + (res.numel() if res is not None else 0)), launch)
     return out
 

@@ -237,8 +237,8 @@ int hkp_bn_from_gram(int32_t k, int32_t c, int64_t count, const double* mean, co
                      int64_t ws_bytes, hkp_stream_t stream);
 /* The kernel a launch with descriptor d runs — its template name as rocprofv3
  * reports it (e.g. "conv_x3_kernel<256, false, false, 16, false, 3>"), for
- * profiling / roofline attribution.  op: HKP_KOP_*; stream_k_ok: whether the
- * call passes a stream-K workspace.  Writes at most len bytes (NUL-terminated);
+ * profiling / roofline attribution — the first launch of hkp_conv_x3_launch_plan.
+ * op: HKP_KOP_*; stream_k_ok: whether the call passes a stream-K workspace.  Writes at most len bytes (NUL-terminated);
  * returns the name's length, or < 0 on bad args. */
 #define HKP_KOP_FWD_X3 0
 #define HKP_KOP_DGRAD_X3 1
@@ -249,6 +249,7 @@ int hkp_bn_from_gram(int32_t k, int32_t c, int64_t count, const double* mean, co
 #define HKP_KOP_FWD_X3_X16 6   /* hkp_conv2d_fwd_x3_products(HKP_X3_X16) */
 #define HKP_KOP_STEM_X3_IMAGE 7     /* hkp_conv2d_fwd_stem_x3_image, fp32 NCHW image */
 #define HKP_KOP_STEM_X3_IMAGE_U8 8  /* hkp_conv2d_fwd_stem_x3_image, uint8 NHWC batch */
+#define HKP_KOP_FWD_F16_BN 9        /* hkp_conv2d_fwd_f16_bn: its fused output BN rules the halo-tile body out */
 int32_t hkp_conv_kernel_name(const hkp_conv_desc* d, int32_t op, int32_t stream_k_ok, char* buf, int32_t len);
 /* Rows per BN statistic tile of a forward conv (op HKP_KOP_FWD_X3 / _W16 / _X16 /
  * _F16) with this descriptor, from the body the launcher picks for it: 96 on the
@@ -257,7 +258,9 @@ int32_t hkp_conv_kernel_name(const hkp_conv_desc* d, int32_t op, int32_t stream_
  * body (the halo-tile body writes 128-row partials).  stat_partials then holds
  * ceil(M / rows) * k * 2 floats, and hkp_bn_finalize / _ws / hkp_bn_stats take
  * tile_rows = rows (src/resnet.py:46,49: the statistics are the same).  For a
- * HKP_TILE_MIX_A3 launch this is the first segment's rows: use the layout below. */
+ * HKP_TILE_MIX_A3 launch this is the first segment's rows: use the layout below.  Any other
+ * op answers 128 (a dgrad, and HKP_KOP_FWD_F16_BN, whose launch writes no partials); the
+ * layout query rejects them. */
 int32_t hkp_conv_x3_stat_tile_rows(const hkp_conv_desc* d, int32_t op);
 /* The BN partial list of that conv as segments: segments[2i] = rows per statistic
  * tile of segment i, segments[2i + 1] = its tiles (room for 3 segments: 6 values);
@@ -277,6 +280,46 @@ int32_t hkp_conv_x3_stat_layout(const hkp_conv_desc* d, int32_t op, int32_t* seg
  * plan, n_tiles > cus) or a negative HKP_ERR_*. */
 #define HKP_MIX_PLAN_LEN 14
 int32_t hkp_conv_x3_mix_plan(int64_t m, int32_t n_tiles, int32_t cus, int32_t* out);
+/* The launches of the conv entry point op (HKP_KOP_*) for descriptor d on cus CUs (0: the
+ * device's, or 256 without a device), with (stream_k_ok) or without a stream-K workspace:
+ * the plan the launcher itself runs (host arithmetic only).  Returns the number of
+ * launches — 1; 2 for the HKP_TILE_256_TAIL form, the full rounds (no blocks, and not
+ * started, where the grid is less than a round) and then conv_x3_tail_kernel; 0 where the
+ * entry point rejects the shape (Cout % 64, no whole line of input channels), launch 0 then
+ * holding only the planner's kernel — or a negative HKP_ERR_*.  For launch launch_index it
+ * writes the kernel's name as hkp_conv_kernel_name does (which names launch 0) and
+ * out[HKP_X3_LAUNCH_PLAN_LEN] = kernel id (HKP_X3K_*; -1: a wgrad kernel) | blocks |
+ * threads | n_tiles (column tiles) | nks (K-steps per tile) | sk_units | sk_one | mt0 |
+ * main_blocks | tail_groups | tail_mt0 | tail_units | mix_b1 | mix_b2 | mix_m1 | mix_m2 |
+ * mix_p1 | mix_p2 | stagger_blocks | DUO stagger in ns (-1: not a DUO launch) | uses the
+ * workspace | workspace bytes it uses | then, the same for every launch: the BN partial
+ * segments (rows, tiles) x 3 | their count | the CU count used | M | 256-row m-tiles | tile
+ * width | tile height.  A strided dgrad runs one such plan per output phase and has no
+ * descriptor here; HKP_KOP_WGRAD_X3 fills the name, blocks, threads and M only.  The BN
+ * partial segments are hkp_conv_x3_stat_layout's when stream_k_ok is set. */
+#define HKP_X3_LAUNCH_PLAN_LEN 34
+#define HKP_X3K_TILE_256 0           /* conv_x3_kernel<256, false, false, 16, false, P> */
+#define HKP_X3K_TILE_128_MF16 1      /* conv_x3_kernel<128, false, false, 16, false, P> */
+#define HKP_X3K_TILE_128_MF32 2      /* conv_x3_kernel<128, false, false, 32, false, P> */
+#define HKP_X3K_PAIR_64 3            /* conv_x3_kernel<64, false, true, 16, false, P> */
+#define HKP_X3K_SK_128 4             /* conv_x3_kernel<128, false, false, 16, true, P> */
+#define HKP_X3K_SK_64 5              /* conv_x3_kernel<64, false, false, 32, true, P> */
+#define HKP_X3K_A3 6                 /* conv_x3_a3_kernel<P> */
+#define HKP_X3K_A3_192 7             /* conv_x3_a3_192_kernel<P> */
+#define HKP_X3K_A3_160 8             /* conv_x3_a3_160_kernel<P> */
+#define HKP_X3K_A3_160X128 9         /* conv_x3_a3_160x128_kernel<P> */
+#define HKP_X3K_A3_MIX 10            /* conv_x3_a3_mix_kernel<P> */
+#define HKP_X3K_TAIL 11              /* conv_x3_tail_kernel<256, P> */
+#define HKP_X3K_HALO 12              /* conv_x3_halo_kernel<P> */
+#define HKP_X3K_HALO_BNIN 13         /* conv_x3_halo_bnin_kernel<P> (hkp_conv2d_fwd_x3_bnin / _f16_bnin) */
+#define HKP_X3K_DUO 14               /* conv_x3_duo_kernel<1> */
+#define HKP_X3K_STEM_PAIR 15         /* conv_x3_kernel<64, true, true, 16, false, 3> */
+#define HKP_X3K_STEM_PATCH 16        /* conv_x3_stem_patch_kernel<0> */
+#define HKP_X3K_STEM_PATCH_IMAGE 17  /* conv_x3_stem_patch_kernel<1> */
+#define HKP_X3K_STEM_PATCH_U8 18     /* conv_x3_stem_patch_kernel<2> */
+#define HKP_X3K_COUNT 19
+int32_t hkp_conv_x3_launch_plan(const hkp_conv_desc* d, int32_t op, int32_t stream_k_ok, int32_t cus,
+                                int32_t launch_index, char* name_buf, int32_t len, int64_t* out);
 
 /* (The A/B instruments — hkp_debug_* — are not part of this library: they exist only
  * in the tools build, include/hulkkp_ab.h.) */
