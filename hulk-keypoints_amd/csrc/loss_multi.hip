@@ -19,6 +19,11 @@
 //                    sums, then dheat) skips the planes that take no part, and a
 //                    one-block kernel sums each plane's partials, ranks, fixes the
 //                    divisor and forms the loss.
+//  * hkp_heat_loss_masked    hkp_heat_loss_planes with a per-pixel ignore mask, uint8 [n][H][W]
+//                    of class bits: a count pass over the mask (the kept pixels of every
+//                    plane), then the planes entry's launches with the mask flag set: a
+//                    masked pixel is selected out of the sum and of dheat, a plane's mean
+//                    and the elements divisor run over the kept pixels.
 //
 // All three losses are one body, heat_loss_walk_kernel, a template over (kind, 16-byte
 // path, mode); the mode says which planes take part and what a block leaves behind:
@@ -112,23 +117,49 @@ __device__ __forceinline__ double loss_divisor(int norm_mode, int a, int pres, d
     return a > 0 ? 1.0 / (hw * (double)a) : 0.0;
 }
 
+// hkp_heat_loss_masked's divisor.  HKP_NORM_ELEMENTS: 1 / the kept pixels of the planes that
+// count (an exact integer), 0 when there is none; HKP_NORM_INSTANCES as loss_divisor.
+__device__ __forceinline__ double masked_divisor(int norm_mode, long long kept, int pres) {
+    if (norm_mode == HKP_NORM_INSTANCES) return 1.0 / (double)(pres > 1 ? pres : 1);
+    return kept > 0 ? 1.0 / (double)kept : 0.0;
+}
+
 // One block, before the pass.  A plane is eligible unless it has no present slot under
 // `ignore`, or weights is given and its weight is not > 0.  inv[0]: the divisor over the
 // eligible planes.  With info / used (hkp_heat_loss_planes; both or neither), per plane:
 // info = bit 0: eligible, the present slots from bit 8 up; used = eligible, which is what
 // holds without top-k (with it, planes_finish_kernel decides `used` and the divisor).
+// MASKED (hkp_heat_loss_masked): npix[p] = the plane's kept pixels, H*W less the set bits
+// of its class that mask_count_kernel counted (cnt [n][mchunks][8], added here: integers,
+// any order); a plane without a kept pixel is not eligible, and HKP_NORM_ELEMENTS divides
+// by the eligible planes' kept pixels.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void planes_count_kernel(int planes, int m, double hw, int ignore, int norm_mode,
                                                           const float* __restrict__ pts,
                                                           const float* __restrict__ weights, int* __restrict__ info,
-                                                          int* __restrict__ used, double* __restrict__ inv) {
+                                                          int* __restrict__ used, double* __restrict__ inv, int k,
+                                                          int mchunks, const int* __restrict__ cnt,
+                                                          int* __restrict__ npix) {
     __shared__ int red[4], redp[4];
+    __shared__ long long redn[4];
     int c = 0, np = 0;
+    long long ne = 0;
     for (int p = threadIdx.x; p < planes; p += 256) {
         const float* rec = pts + (long)p * 3 * m;
         int on = 0;
         for (int j = 0; j < m; ++j) on += rec[3 * j + 2] > 0.f ? 1 : 0;
         bool el = !(ignore && on == 0);
         if (weights != nullptr && !(weights[p] > 0.f)) el = false;
+        if constexpr (MASKED) {
+            const int b = p / k, cl = p - b * k;
+            const int* cb = cnt + (long)b * mchunks * 8 + cl;
+            int set = 0;
+            for (int j = 0; j < mchunks; ++j) set += cb[8 * j];
+            const int kept = (int)hw - set;
+            npix[p] = kept;
+            if (kept <= 0) el = false;
+            ne += el ? kept : 0;
+        }
         if (info != nullptr) {
             info[p] = (el ? 1 : 0) | (on << 8);
             used[p] = el ? 1 : 0;
@@ -140,14 +171,61 @@ __global__ __launch_bounds__(256) void planes_count_kernel(int planes, int m, do
     for (int o = 32; o > 0; o >>= 1) {
         c += __shfl_xor(c, o);
         np += __shfl_xor(np, o);
+        if constexpr (MASKED) ne += __shfl_xor(ne, o);
     }
     if ((threadIdx.x & 63) == 0) {
         red[threadIdx.x >> 6] = c;
         redp[threadIdx.x >> 6] = np;
+        if constexpr (MASKED) redn[threadIdx.x >> 6] = ne;
     }
     __syncthreads();
-    if (threadIdx.x == 0)
-        inv[0] = loss_divisor(norm_mode, red[0] + red[1] + red[2] + red[3], redp[0] + redp[1] + redp[2] + redp[3], hw);
+    if (threadIdx.x == 0) {
+        if constexpr (MASKED)
+            inv[0] = masked_divisor(norm_mode, redn[0] + redn[1] + redn[2] + redn[3],
+                                    redp[0] + redp[1] + redp[2] + redp[3]);
+        else
+            inv[0] = loss_divisor(norm_mode, red[0] + red[1] + red[2] + red[3], redp[0] + redp[1] + redp[2] + redp[3], hw);
+    }
+}
+
+// The set bits of every class in a slice of one image's mask: block (image, chunk) leaves
+// cnt[image][chunk][8].  An item is 4 bytes, one 32-bit load when the image's bytes are
+// 4-byte aligned (WORD), 4 bounded byte loads otherwise.
+constexpr int MASK_MAX_K = 8;
+template <bool WORD>
+__global__ __launch_bounds__(256) void mask_count_kernel(int HW, int mchunks, const uint8_t* __restrict__ mask,
+                                                        int* __restrict__ cnt) {
+    __shared__ int red[4][8];
+    const int b = blockIdx.x / mchunks, chunk = blockIdx.x - b * mchunks;
+    const uint8_t* mi = mask + (long)b * HW;
+    const int items = (HW + 3) >> 2;
+    int s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int q = chunk * 256 + threadIdx.x; q < items; q += mchunks * 256) {
+        uint32_t w;
+        if constexpr (WORD) {
+            w = ((const uint32_t*)mi)[q];
+        } else {
+            w = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < HW) w |= (uint32_t)mi[4 * q + e] << (8 * e);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] += __popc(w & (0x01010101u << j));
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[j] += __shfl_xor(s[j], o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[threadIdx.x >> 6][j] = s[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8)
+        cnt[(long)blockIdx.x * 8 + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
 constexpr int WALK_EX = 0, PL_ALL = 1, PL_SUMS = 2, PL_GRAD = 3;   // the header has what each means
@@ -156,7 +234,11 @@ constexpr int WALK_EX = 0, PL_ALL = 1, PL_SUMS = 2, PL_GRAD = 3;   // the header
 // row.  ignore and inv_n_host are read by WALK_EX alone (inv_n_dev, when set, goes before
 // inv_n_host); info, used and weights by the PL_ modes alone, and they come last so that
 // WALK_EX keeps the argument offsets it was measured with ("One body").
-template <int EK, bool VEC4, int MODE>
+// MASKED (PL_ modes, hkp_heat_loss_masked): bit (plane % k) of mask[image][pixel] takes the
+// pixel out: its term and its dheat are +0 by a select, whatever its heat holds.  Under
+// VEC4 the 4 mask bytes of an item are one 32-bit load when the mask base is 4-byte
+// aligned (W % 4 == 0 holds), 4 byte loads otherwise.  mask and k are the last arguments.
+template <int EK, bool VEC4, int MODE, bool MASKED = false>
 __global__ __launch_bounds__(256) void heat_loss_walk_kernel(int m, int H, int W, int chunks, float den, int ignore,
                                                             float betaf, double inv_n_host,
                                                             const double* __restrict__ inv_n_dev,
@@ -164,7 +246,9 @@ __global__ __launch_bounds__(256) void heat_loss_walk_kernel(int m, int H, int W
                                                             const float* __restrict__ pts, float* __restrict__ dheat,
                                                             double* __restrict__ part, const int* __restrict__ info,
                                                             const int* __restrict__ used,
-                                                            const float* __restrict__ weights) {
+                                                            const float* __restrict__ weights,
+                                                            const uint8_t* __restrict__ mask, int k) {
+    static_assert(!MASKED || MODE != WALK_EX, "the mask goes with the planes modes");
     __shared__ float su[MULTI_MAX_M], sv[MULTI_MAX_M];
     __shared__ int scnt;
     __shared__ double red[4];
@@ -201,11 +285,30 @@ __global__ __launch_bounds__(256) void heat_loss_walk_kernel(int m, int H, int W
     const double wd = (MODE != WALK_EX && weights) ? (double)weights[plane] : 1.0;
     const double beta = (double)betaf, bm1 = beta - 1.0;
     double acc = 0.0;
+    const uint8_t* mi = nullptr;
+    int cbit = 0;
+    bool mword = false;
+    if constexpr (MASKED) {
+        const long img = plane / k;
+        cbit = (int)(plane - img * k);
+        mi = mask + img * (long)HW;
+        mword = ((uintptr_t)mi & 3) == 0;
+    }
     if constexpr (VEC4) {
         const int W4 = W >> 2;
         for (int q = first; q < (HW >> 2); q += step) {
             const int yy = q / W4, x0 = (q - yy * W4) * 4;
             const f32x4 xv = ((const f32x4*)pp)[q];
+            uint32_t mw = 0;
+            if constexpr (MASKED) {
+                if (mword) {
+                    mw = ((const uint32_t*)mi)[q];
+                } else {
+                    const uint8_t* mb = mi + 4 * (long)q;
+                    mw = (uint32_t)mb[0] | ((uint32_t)mb[1] << 8) | ((uint32_t)mb[2] << 16) | ((uint32_t)mb[3] << 24);
+                }
+                mw >>= cbit;
+            }
             float t[4] = {0.f, 0.f, 0.f, 0.f};
             for (int j = 0; j < cnt; ++j) {   // target_at for 4 pixels of a row: dy once
                 const float u = su[j];
@@ -221,8 +324,15 @@ __global__ __launch_bounds__(256) void heat_loss_walk_kernel(int m, int H, int W
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 double g;
-                acc += loss_elem<EK>((double)xv[e], (double)t[e], inv_n, beta, bm1, &g);
-                gv[e] = MODE == WALK_EX ? (float)g : (float)(g * wd);
+                const double l = loss_elem<EK>((double)xv[e], (double)t[e], inv_n, beta, bm1, &g);
+                if constexpr (MASKED) {
+                    const bool keep = !((mw >> (8 * e)) & 1u);
+                    acc += keep ? l : 0.0;
+                    gv[e] = keep ? (float)(g * wd) : 0.f;
+                } else {
+                    acc += l;
+                    gv[e] = MODE == WALK_EX ? (float)g : (float)(g * wd);
+                }
             }
             if (dp) ((f32x4*)dp)[q] = gv;
         }
@@ -231,8 +341,15 @@ __global__ __launch_bounds__(256) void heat_loss_walk_kernel(int m, int H, int W
             const int yy = i / W;
             const float t = target_at(i - yy * W, yy, cnt, su, sv, den);
             double g;
-            acc += loss_elem<EK>((double)pp[i], (double)t, inv_n, beta, bm1, &g);
-            if (dp) dp[i] = MODE == WALK_EX ? (float)g : (float)(g * wd);
+            const double l = loss_elem<EK>((double)pp[i], (double)t, inv_n, beta, bm1, &g);
+            if constexpr (MASKED) {
+                const bool keep = !((mi[i] >> cbit) & 1);
+                acc += keep ? l : 0.0;
+                if (dp) dp[i] = keep ? (float)(g * wd) : 0.f;
+            } else {
+                acc += l;
+                if (dp) dp[i] = MODE == WALK_EX ? (float)g : (float)(g * wd);
+            }
         }
     }
     if constexpr (MODE != PL_GRAD) {
@@ -266,13 +383,20 @@ __device__ __forceinline__ bool planes_ahead(double rq, int cq, double rp, int c
 // the two sequential sums wait for one global load each, not one per term.
 constexpr int PLANES_STAGE = 4096;   // at least MULTI_CHUNKS planes' partials
 
+// MASKED: a plane's mean, in plane_loss and in the ranking, is S over its kept pixels
+// (npix), the divisor of HKP_NORM_ELEMENTS the counted planes' kept pixels, and
+// plane_pixels gets npix (0 for a plane that is not eligible).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void planes_finish_kernel(int planes, int k, int chunks, int topk, double hw,
                                                            int norm_mode, const float* __restrict__ weights,
                                                            const int* __restrict__ info, int* used,
                                                            const double* __restrict__ part, double* S, double* inv,
                                                            double* loss, double* __restrict__ plane_loss,
-                                                           int32_t* __restrict__ plane_used) {
+                                                           int32_t* __restrict__ plane_used,
+                                                           const int* __restrict__ npix,
+                                                           int32_t* __restrict__ plane_pixels) {
     __shared__ int red[4], redp[4];
+    __shared__ long long redn[4];
     __shared__ double stage[PLANES_STAGE];
     const int tile = PLANES_STAGE / chunks;          // planes per trip, >= 64
     for (int p0 = 0; p0 < planes; p0 += tile) {
@@ -295,12 +419,13 @@ __global__ __launch_bounds__(256) void planes_finish_kernel(int planes, int k, i
             int u = 0;
             if (info[p] & 1) {
                 const int b = p / k, c = p - b * k;
-                const double r = (weights ? (double)weights[p] : 1.0) * S[p];
+                const double r = (weights ? (double)weights[p] : 1.0) * (MASKED ? S[p] / (double)npix[p] : S[p]);
                 int ahead = 0;
                 for (int cq = 0; cq < k; ++cq) {
                     const int q = b * k + cq;
                     if (cq == c || !(info[q] & 1)) continue;
-                    const double rq = (weights ? (double)weights[q] : 1.0) * S[q];
+                    const double rq =
+                        (weights ? (double)weights[q] : 1.0) * (MASKED ? S[q] / (double)npix[q] : S[q]);
                     ahead += planes_ahead(rq, cq, r, c) ? 1 : 0;
                 }
                 u = ahead < topk ? 1 : 0;
@@ -310,21 +435,30 @@ __global__ __launch_bounds__(256) void planes_finish_kernel(int planes, int k, i
         __syncthreads();
     }
     int cn = 0, np = 0;
+    long long ne = 0;
     for (int p = threadIdx.x; p < planes; p += 256) {
         const int el = info[p] & 1, u = used[p];
         cn += u;
         np += u ? (info[p] >> 8) : 0;
-        if (plane_loss) plane_loss[p] = el ? S[p] / hw : -1.0;
+        if constexpr (MASKED) {
+            ne += u ? npix[p] : 0;
+            if (plane_loss) plane_loss[p] = el ? S[p] / (double)npix[p] : -1.0;
+            if (plane_pixels) plane_pixels[p] = el ? npix[p] : 0;
+        } else {
+            if (plane_loss) plane_loss[p] = el ? S[p] / hw : -1.0;
+        }
         if (plane_used) plane_used[p] = u;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         cn += __shfl_xor(cn, o);
         np += __shfl_xor(np, o);
+        if constexpr (MASKED) ne += __shfl_xor(ne, o);
     }
     if ((threadIdx.x & 63) == 0) {
         red[threadIdx.x >> 6] = cn;
         redp[threadIdx.x >> 6] = np;
+        if constexpr (MASKED) redn[threadIdx.x >> 6] = ne;
     }
     // a plane that is not counted adds +0.0, which leaves a sum of terms >= 0 (or NaN) as it is
     double t = 0.0;
@@ -339,8 +473,12 @@ __global__ __launch_bounds__(256) void planes_finish_kernel(int planes, int k, i
         }
     }
     if (threadIdx.x == 0) {
-        const double d =
-            loss_divisor(norm_mode, red[0] + red[1] + red[2] + red[3], redp[0] + redp[1] + redp[2] + redp[3], hw);
+        double d;
+        if constexpr (MASKED)
+            d = masked_divisor(norm_mode, redn[0] + redn[1] + redn[2] + redn[3],
+                               redp[0] + redp[1] + redp[2] + redp[3]);
+        else
+            d = loss_divisor(norm_mode, red[0] + red[1] + red[2] + red[3], redp[0] + redp[1] + redp[2] + redp[3], hw);
         inv[0] = d;
         loss[0] = t * d;
     }
@@ -364,6 +502,11 @@ struct LossPlan {
     float* dheat;
     double *inv_dev, *part;
     int *info, *used;
+    // hkp_heat_loss_masked's own: the mask, its classes, the count pass's chunks and partial
+    // counts, the kept pixels per plane
+    const uint8_t* mask;
+    int k, mchunks;
+    int *cnt, *npix;
 };
 
 // `who` is the entry's name in the error texts, qfl_ok whether it knows HKP_LOSS_QFL
@@ -400,19 +543,29 @@ static int loss_plan(const char* who, bool qfl_ok, int32_t n, int32_t k, int32_t
 }
 
 static void launch_count(const LossPlan& lp, hipStream_t st) {
-    hipLaunchKernelGGL(planes_count_kernel, dim3(1), dim3(256), 0, st, lp.planes, lp.m, lp.hw, lp.ignore, lp.norm_mode,
-                       lp.pts, lp.weights, lp.info, lp.used, lp.inv_dev);
+    if (lp.mask)
+        hipLaunchKernelGGL(planes_count_kernel<true>, dim3(1), dim3(256), 0, st, lp.planes, lp.m, lp.hw, lp.ignore,
+                           lp.norm_mode, lp.pts, lp.weights, lp.info, lp.used, lp.inv_dev, lp.k, lp.mchunks, lp.cnt,
+                           lp.npix);
+    else
+        hipLaunchKernelGGL(planes_count_kernel<false>, dim3(1), dim3(256), 0, st, lp.planes, lp.m, lp.hw, lp.ignore,
+                           lp.norm_mode, lp.pts, lp.weights, lp.info, lp.used, lp.inv_dev, 0, 0, nullptr, nullptr);
 }
 
 // the one (kind x 16-byte path x mode) dispatch; inv_n_dev: where the pass reads its
 // divisor (WALK_EX: null for the host's)
 static void launch_walk(const LossPlan& lp, int mode, const double* inv_n_dev, hipStream_t st) {
-#define HKP_WALK(EK, V4, MD)                                                                                        \
-    hipLaunchKernelGGL((heat_loss_walk_kernel<EK, V4, MD>), dim3((unsigned)lp.nblocks), dim3(256), 0, st, lp.m, lp.H, \
-                       lp.W, lp.chunks, lp.den, lp.ignore, lp.beta, lp.inv_n, inv_n_dev, lp.heat, lp.pts, lp.dheat,   \
-                       lp.part, lp.info, lp.used, lp.weights)
+#define HKP_WALK(EK, V4, MD, MK)                                                                                   \
+    hipLaunchKernelGGL((heat_loss_walk_kernel<EK, V4, MD, MK>), dim3((unsigned)lp.nblocks), dim3(256), 0, st, lp.m,  \
+                       lp.H, lp.W, lp.chunks, lp.den, lp.ignore, lp.beta, lp.inv_n, inv_n_dev, lp.heat, lp.pts,      \
+                       lp.dheat, lp.part, lp.info, lp.used, lp.weights, lp.mask, lp.k)
+#define HKP_WALK_M(EK, V4, MD)                             \
+    if constexpr (MD != WALK_EX) {                         \
+        if (lp.mask) HKP_WALK(EK, V4, MD, true);           \
+        else HKP_WALK(EK, V4, MD, false);                  \
+    } else HKP_WALK(EK, V4, MD, false)
 #define HKP_WALK_V(EK, MD) \
-    if (lp.vec4) HKP_WALK(EK, true, MD); else HKP_WALK(EK, false, MD)
+    if (lp.vec4) { HKP_WALK_M(EK, true, MD); } else { HKP_WALK_M(EK, false, MD); }
 #define HKP_WALK_K(MD)                                \
     switch (lp.ek) {                                  \
         case EK_BCE: HKP_WALK_V(EK_BCE, MD); break;   \
@@ -428,6 +581,7 @@ static void launch_walk(const LossPlan& lp, int mode, const double* inv_n_dev, h
     }
 #undef HKP_WALK_K
 #undef HKP_WALK_V
+#undef HKP_WALK_M
 #undef HKP_WALK
 }
 
@@ -520,12 +674,67 @@ extern "C" int hkp_heat_loss_planes(int32_t n, int32_t k, int32_t m, int32_t H, 
     HKP_LAUNCH_CHECK("hkp_heat_loss_planes(prepare)");
     launch_walk(lp, topk == 0 ? PL_ALL : PL_SUMS, lp.inv_dev, st);
     HKP_LAUNCH_CHECK("hkp_heat_loss_planes");
-    hipLaunchKernelGGL(planes_finish_kernel, dim3(1), dim3(256), 0, st, lp.planes, k, lp.chunks, topk, lp.hw, norm_mode,
-                       weights, lp.info, lp.used, lp.part, S, lp.inv_dev, loss, plane_loss, plane_used);
+    hipLaunchKernelGGL(planes_finish_kernel<false>, dim3(1), dim3(256), 0, st, lp.planes, k, lp.chunks, topk, lp.hw,
+                       norm_mode, weights, lp.info, lp.used, lp.part, S, lp.inv_dev, loss, plane_loss, plane_used,
+                       nullptr, nullptr);
     HKP_LAUNCH_CHECK("hkp_heat_loss_planes(finish)");
     if (topk > 0 && dheat != nullptr) {
         launch_walk(lp, PL_GRAD, lp.inv_dev, st);
         HKP_LAUNCH_CHECK("hkp_heat_loss_planes(dheat)");
+    }
+    return HKP_OK;
+}
+
+// the planes entry's workspace, then npix per plane and the count pass's partial counts
+// [n][MULTI_CHUNKS][8] (int32)
+extern "C" int64_t hkp_heat_loss_masked_workspace(int32_t n, int32_t k, int32_t H, int32_t W) {
+    const int64_t base = hkp_heat_loss_planes_workspace(n, k, H, W);
+    if (base < 0) return -1;
+    const int64_t ints = (int64_t)n * k + (int64_t)n * MULTI_CHUNKS * 8;
+    return base + (ints + 1) / 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int hkp_heat_loss_masked(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                                    int32_t absent_mode, int32_t norm_mode, float beta, int32_t topk,
+                                    const float* heat, const float* pts, const float* weights, const uint8_t* mask,
+                                    float sigma, double* loss, float* dheat, double* plane_loss, int32_t* plane_used,
+                                    int32_t* plane_pixels, void* workspace, hkp_stream_t stream) {
+    HKP_CHECK_ARG(mask != nullptr, "hkp_heat_loss_masked: null mask (hkp_heat_loss_planes is the entry without one)");
+    HKP_CHECK_ARG(k <= MASK_MAX_K, "hkp_heat_loss_masked: k = %d classes, a mask byte holds %d", k, MASK_MAX_K);
+    LossPlan lp;
+    const int rc = loss_plan("hkp_heat_loss_masked", true, n, k, m, H, W, loss_kind, absent_mode, norm_mode, beta, heat,
+                             pts, sigma, loss, dheat, workspace, &lp);
+    if (rc != HKP_OK) return rc;
+    HKP_CHECK_ARG(topk >= 0 && topk <= k, "hkp_heat_loss_masked: topk %d outside 0..k (k = %d)", topk, k);
+    double* S = lp.part + (long)lp.planes * MULTI_CHUNKS;
+    lp.weights = weights;
+    lp.info = (int*)(S + lp.planes);
+    lp.used = lp.info + lp.planes;
+    // (past the planes entry's workspace, which ends on a multiple of 8 bytes)
+    lp.npix = (int*)((char*)workspace + hkp_heat_loss_planes_workspace(n, k, H, W));
+    lp.cnt = lp.npix + lp.planes;
+    lp.mask = mask, lp.k = k;
+    const int HW = H * W;
+    lp.mchunks = multi_chunks(((long)HW + 3) / 4);
+    hipStream_t st = as_stream(stream);
+    if (HW % 4 == 0 && ((uintptr_t)mask & 3) == 0)
+        hipLaunchKernelGGL(mask_count_kernel<true>, dim3((unsigned)(n * lp.mchunks)), dim3(256), 0, st, HW, lp.mchunks,
+                           mask, lp.cnt);
+    else
+        hipLaunchKernelGGL(mask_count_kernel<false>, dim3((unsigned)(n * lp.mchunks)), dim3(256), 0, st, HW, lp.mchunks,
+                           mask, lp.cnt);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_masked(count)");
+    launch_count(lp, st);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_masked(prepare)");
+    launch_walk(lp, topk == 0 ? PL_ALL : PL_SUMS, lp.inv_dev, st);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_masked");
+    hipLaunchKernelGGL(planes_finish_kernel<true>, dim3(1), dim3(256), 0, st, lp.planes, k, lp.chunks, topk, lp.hw,
+                       norm_mode, weights, lp.info, lp.used, lp.part, S, lp.inv_dev, loss, plane_loss, plane_used,
+                       lp.npix, plane_pixels);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_masked(finish)");
+    if (topk > 0 && dheat != nullptr) {
+        launch_walk(lp, PL_GRAD, lp.inv_dev, st);
+        HKP_LAUNCH_CHECK("hkp_heat_loss_masked(dheat)");
     }
     return HKP_OK;
 }

@@ -123,6 +123,47 @@ static void warp_launch(bool dword, dim3 grid, hipStream_t s, int hs, int ws, co
         hipLaunchKernelGGL((warp_affine_u8_kernel<INTERP, BORDER, false>), grid, dim3(256), 0, s, hs, ws, in, h, w, out, xf);
 }
 
+// hkp_warp_mask_u8: one channel, warp_pixel's NEAREST rule (the same two helpers), the
+// source byte through the image's table, the fill byte as given.  The block, tile and
+// store paths are the image warp's.
+template <int BORDER, bool DWORD>
+__global__ __launch_bounds__(256) void warp_mask_u8_kernel(int hs, int ws, const uint8_t* __restrict__ in, int h, int w,
+                                                          uint8_t* __restrict__ out,
+                                                          const hkp_warp_xform* __restrict__ xforms, int fill,
+                                                          const uint8_t* __restrict__ lut) {
+    const int tid = threadIdx.x, n = blockIdx.z;
+    const int x = blockIdx.x * WARP_TW + (tid % (WARP_TW / WARP_PX)) * WARP_PX;
+    const int y = blockIdx.y * WARP_TH + tid / (WARP_TW / WARP_PX);
+    if (x >= w || y >= h) return;
+    const hkp_warp_xform& xf = xforms[n];                    // block-uniform
+    const int64_t m0 = xf.m[0], m3 = xf.m[3];
+    int64_t sx = m0 * x + (int64_t)xf.m[1] * y + xf.m[2];
+    int64_t sy = m3 * x + (int64_t)xf.m[4] * y + xf.m[5];
+    const uint8_t* src = in + (size_t)n * hs * ws;
+    const uint8_t* tab = lut ? lut + (size_t)n * 256 : nullptr;
+    uint8_t* dst = out + ((size_t)n * h + y) * w + x;
+    int px[WARP_PX];
+#pragma unroll
+    for (int j = 0; j < WARP_PX; ++j) {
+        bool ox, oy;
+        const int ix = warp_tap<BORDER>(warp_clamp_coord((sx + 32768) >> 16, ws), ws, ox);
+        const int iy = warp_tap<BORDER>(warp_clamp_coord((sy + 32768) >> 16, hs), hs, oy);
+        int v = src[(size_t)iy * ws + ix];
+        if (tab) v = tab[v];
+        if (BORDER == HKP_WARP_BORDER_CONSTANT && (ox || oy)) v = fill;
+        px[j] = v;
+        sx += m0;
+        sy += m3;
+    }
+    if (DWORD) {                                             // w % 4 == 0, out 4-byte aligned: x + 3 < w
+        *(uint32_t*)dst = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < WARP_PX; ++j)
+            if (x + j < w) dst[j] = (uint8_t)px[j];
+    }
+}
+
 }  // namespace hkp
 
 using namespace hkp;
@@ -162,5 +203,45 @@ extern "C" int hkp_warp_affine_u8(int32_t n, int32_t hs, int32_t ws, const uint8
     HKP_WARP_CASE(HKP_WARP_NEAREST, HKP_WARP_BORDER_REFLECT101);
 #undef HKP_WARP_CASE
     HKP_LAUNCH_CHECK("hkp_warp_affine_u8");
+    return HKP_OK;
+}
+
+extern "C" int hkp_warp_mask_u8(int32_t n, int32_t hs, int32_t ws, const uint8_t* mask_in, int32_t h, int32_t w,
+                                uint8_t* mask_out, const hkp_warp_xform* xforms_host, const hkp_warp_xform* xforms,
+                                int32_t border, int32_t fill, const uint8_t* lut, hkp_stream_t stream) {
+    HKP_CHECK_ARG(n >= 1 && n <= 65535, "hkp_warp_mask_u8: bad batch size n=%d (1..65535)", n);
+    HKP_CHECK_ARG(hs >= 1 && hs <= HKP_WARP_MAX_DIM && ws >= 1 && ws <= HKP_WARP_MAX_DIM,
+                  "hkp_warp_mask_u8: source %dx%d outside 1..%d", hs, ws, HKP_WARP_MAX_DIM);
+    HKP_CHECK_ARG(h >= 1 && h <= HKP_WARP_MAX_DIM && w >= 1 && w <= HKP_WARP_MAX_DIM,
+                  "hkp_warp_mask_u8: output %dx%d outside 1..%d", h, w, HKP_WARP_MAX_DIM);
+    HKP_CHECK_ARG(border >= HKP_WARP_BORDER_CONSTANT && border <= HKP_WARP_BORDER_REFLECT101,
+                  "hkp_warp_mask_u8: unknown border mode %d", border);
+    HKP_CHECK_ARG(border != HKP_WARP_BORDER_REFLECT101 || (hs >= 2 && ws >= 2),
+                  "hkp_warp_mask_u8: REFLECT101 needs a source of at least 2x2, got %dx%d", hs, ws);
+    HKP_CHECK_ARG(fill >= 0 && fill <= 255, "hkp_warp_mask_u8: fill %d outside 0..255", fill);
+    HKP_CHECK_ARG(mask_in && mask_out && xforms_host && xforms, "hkp_warp_mask_u8: null pointer");
+    HKP_CHECK_ARG(((uintptr_t)xforms & 3) == 0, "hkp_warp_mask_u8: xforms must be 4-byte aligned");
+    const int64_t in_bytes = (int64_t)n * hs * ws, out_bytes = (int64_t)n * h * w;
+    HKP_CHECK_ARG(mask_out + out_bytes <= mask_in || mask_in + in_bytes <= mask_out,
+                  "hkp_warp_mask_u8: mask_out must not overlap mask_in (taps are gathered)");
+    for (int32_t i = 0; i < n; ++i)
+        HKP_CHECK_ARG(xforms_host[i].reserved == 0, "hkp_warp_mask_u8: transform %d has a non-zero reserved field", i);
+    const bool dword = w % 4 == 0 && ((uintptr_t)mask_out & 3) == 0;
+    const dim3 grid((unsigned)((w + WARP_TW - 1) / WARP_TW), (unsigned)((h + WARP_TH - 1) / WARP_TH), (unsigned)n);
+    const hipStream_t s = as_stream(stream);
+#define HKP_WARP_MASK_CASE(B)                                                                                          \
+    if (border == B) {                                                                                                 \
+        if (dword)                                                                                                     \
+            hipLaunchKernelGGL((warp_mask_u8_kernel<B, true>), grid, dim3(256), 0, s, hs, ws, mask_in, h, w, mask_out,  \
+                               xforms, fill, lut);                                                                     \
+        else                                                                                                           \
+            hipLaunchKernelGGL((warp_mask_u8_kernel<B, false>), grid, dim3(256), 0, s, hs, ws, mask_in, h, w, mask_out, \
+                               xforms, fill, lut);                                                                     \
+    }
+    HKP_WARP_MASK_CASE(HKP_WARP_BORDER_CONSTANT)
+    HKP_WARP_MASK_CASE(HKP_WARP_BORDER_REPLICATE)
+    HKP_WARP_MASK_CASE(HKP_WARP_BORDER_REFLECT101)
+#undef HKP_WARP_MASK_CASE
+    HKP_LAUNCH_CHECK("hkp_warp_mask_u8");
     return HKP_OK;
 }

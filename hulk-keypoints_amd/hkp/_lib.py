@@ -93,6 +93,11 @@ assert ctypes.sizeof(AugStage) == 32 and ctypes.sizeof(AugProgram) == 288
 HKP_WARP_BILINEAR, HKP_WARP_NEAREST = 0, 1
 HKP_WARP_BORDER_CONSTANT, HKP_WARP_BORDER_REPLICATE, HKP_WARP_BORDER_REFLECT101 = 0, 1, 2
 HKP_WARP_MAX_DIM = 16384
+# the ignore masks' ABI (include/hulkkp.h)
+HKP_MASK_BOX, HKP_MASK_DISC = 1, 2
+HKP_MASK_MAX_REGIONS = 64
+HKP_MASK_MAX_DIM = 4096
+MASK_MAX_K = 8                     # class bits of a mask byte (hkp_heat_loss_masked)
 
 
 class WarpXform(ctypes.Structure):
@@ -258,6 +263,11 @@ SIGNATURES = {
     "hkp_heat_loss_planes_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "hkp_heat_loss_planes": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _F,
                                             _P, _P, _P, _P, _P, _P]),
+    # ... with a per-pixel ignore mask uint8 [n,H,W] of class bits (mask after weights; plane_pixels after
+    # plane_used)
+    "hkp_heat_loss_masked_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "hkp_heat_loss_masked": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _P,
+                                            _F, _P, _P, _P, _P, _P, _P, _P]),
     # evaluation: peaks/counts of hkp_heat_peaks against pts (thresholds: float array on the host)
     "hkp_peaks_match": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_F), _P, _P, _P, _P, _P, _P,
                                        _P, _P, _P]),
@@ -273,6 +283,11 @@ SIGNATURES = {
     # affine warp (xforms_host: WarpXform array on the host, xforms: its device copy)
     "hkp_warp_affine_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(WarpXform), _P, _I32,
                                           _I32, _P]),
+    # ignore masks: the one-channel nearest warp (border, fill byte, lut [n,256] or null) and the rasteriser
+    # of region records (regions fp32 [n,r,6] on the device)
+    "hkp_warp_mask_u8": (ctypes.c_int, [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(WarpXform), _P, _I32, _I32,
+                                        _P, _P]),
+    "hkp_mask_regions_u8": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P]),
     # antialiased resize (records_host / tables_host: host copies, validated; records / tables: device copies)
     "hkp_resample_u8": (ctypes.c_int, [_I32, _P, _I64, ctypes.POINTER(ResampleImage), _P, _P, _P, _I64, _I32, _I32,
                                        _P, _P]),

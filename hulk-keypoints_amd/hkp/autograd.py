@@ -94,8 +94,27 @@ class _HeatLossPlanesFn(torch.autograd.Function):
         return (dheat * g.to(dheat.dtype),) + (None,) * 8
 
 
+class _HeatLossMaskedFn(torch.autograd.Function):
+    """ops.heat_loss_masked (heat_loss_planes with a per-pixel ignore mask); the per-plane
+    values leave as non-differentiable outputs."""
+
+    @staticmethod
+    def forward(ctx, heat, pts, sigma, kind, absent, beta, norm, weights, topk, mask):
+        loss, dheat, plane_loss, plane_used, plane_pixels = ops.heat_loss_masked(
+            heat.contiguous(), pts, mask, sigma, kind, absent,
+            want_grad=torch.is_grad_enabled() or heat.requires_grad, beta=beta, norm=norm, weights=weights, topk=topk)
+        ctx.save_for_backward(dheat)
+        ctx.mark_non_differentiable(plane_loss, plane_used, plane_pixels)
+        return loss, plane_loss, plane_used, plane_pixels
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gu, _gp):
+        (dheat,) = ctx.saved_tensors
+        return (dheat * g.to(dheat.dtype),) + (None,) * 9
+
+
 def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero", beta=2.0,
-                 norm="elements", weights=None, topk=None, return_planes=False):
+                 norm="elements", weights=None, topk=None, return_planes=False, mask=None):
     """mean BCE (default) or MSE between fp32 heatmaps and the fp64 Gaussian target
     (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor.
     ``pts`` [N,K,M,3] (u, v, flag) in place of both: the multi-instance target
@@ -108,7 +127,20 @@ def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, ab
     ops.heat_loss_planes: a weight per (image, class) plane (not > 0: the plane is not
     labelled and leaves the loss), per image only the ``topk`` planes with the largest
     weighted loss, and with ``return_planes`` the result is (loss, plane_loss [N,K] f64,
-    plane_used [N,K] int32), the two extras detached."""
+    plane_used [N,K] int32), the two extras detached.
+    ``mask`` uint8 [N,H,W] (``uv`` or ``pts`` labels, K <= 8): the per-pixel ignore mask of
+    ops.heat_loss_masked, bit c of a byte taking that pixel out for class c; with
+    ``return_planes`` a fourth value follows, plane_pixels [N,K] int32."""
+    if mask is not None:
+        if target is not None or (pts is None) == (uv is None):
+            raise ops.HkpError("heatmap_loss: a mask needs pts or uv labels alone; a dense target is not supported")
+        ops._loss_choice("heatmap_loss", kind, norm, beta)
+        ops._planes_choice("heatmap_loss", weights, topk, heat)
+        ops._mask_choice("heatmap_loss", mask, heat)
+        if pts is None:
+            pts, absent = ops._uv_as_pts(heat, uv), "zero"
+        out = _HeatLossMaskedFn.apply(heat, pts, sigma, kind, absent, beta, norm, weights, topk, mask)
+        return out if return_planes else out[0]
     if weights is not None or topk is not None or return_planes:
         if target is not None or (pts is None) == (uv is None):
             raise ops.HkpError("heatmap_loss: weights, topk and return_planes need pts or uv labels alone; a dense "

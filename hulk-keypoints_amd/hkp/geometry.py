@@ -151,6 +151,35 @@ class WarpPlan:
             self._dev[key] = got
         return got[0]
 
+    def mask_lut(self, device):
+        """uint8 [n, 256] on `device`, or None when no image needs a table: hkp.masks.flip_lut
+        of `flip_pairs` for the flipped images, the identity for the others.  Uploaded from
+        pinned memory on the current stream and cached on the plan like device_array()."""
+        if not self.flip_pairs or not self.flipped.any():
+            return None
+        device = torch.device(device)
+        key = ("lut", device.index if device.index is not None else torch.cuda.current_device())
+        got = self._dev.get(key)
+        if got is None:
+            from .masks import flip_lut
+            ident, swap = flip_lut(()), flip_lut(self.flip_pairs)
+            pin = torch.stack([swap if f else ident for f in self.flipped]).pin_memory()
+            got = (pin.to(torch.device("cuda", key[1]), non_blocking=True), pin)
+            self._dev[key] = got
+        return got[0]
+
+    def apply_mask(self, mask, fill=0):
+        """An ignore mask (hkp.masks: uint8 [n, Hs, Ws] class bits, on the device) through
+        the batch's transforms -> uint8 [n, h, w] in the warped images' frame
+        (ops.warp_mask_u8).  The plan's matrices and border are used; `interp` is not: a mask
+        is always sampled nearest.  Where the image was flipped, the class bits of
+        `flip_pairs` are exchanged, as apply_points exchanges the label rows.  fill: the byte
+        outside the source under border="constant" (0: trained, 255: ignored)."""
+        from . import ops
+        if not isinstance(mask, torch.Tensor):
+            raise HkpError("apply_mask: expected a uint8 tensor [%d, H, W] on the device" % self.n)
+        return ops.warp_mask_u8(mask, self, fill=fill, lut=self.mask_lut(mask.device))
+
     def apply_uv(self, uv):
         """Labels through the batch's transforms: uv [n, K, 2] on the host (numpy or
         a CPU tensor; the same kind comes back, float32) -> forward matrix, rows of

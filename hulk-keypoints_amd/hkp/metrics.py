@@ -169,10 +169,12 @@ class KeypointMetrics:
         self.hist.zero_()
         self.totals.zero_()
 
-    def update(self, peaks, counts, labels):
+    def update(self, peaks, counts, labels, mask=None):
         """One launch, no synchronisation: peaks / counts as ops.heat_peaks returns
         them, labels [B,K,M,3] (u, v, flag) or [B,K,2], all on the accumulators'
-        device."""
+        device.  mask uint8 [B,H,W] (hkp.masks, in the peaks' frame): the peaks on ignored
+        pixels are dropped first (masks.peaks_drop_masked: they are neither true nor false
+        positives, COCO's rule for ignore regions); still no synchronisation."""
         if not isinstance(peaks, torch.Tensor):
             raise HkpError("KeypointMetrics.update: expected tensors")
         if peaks.dim() == 4 and peaks.shape[1] != self.num_keypoints:
@@ -180,6 +182,9 @@ class KeypointMetrics:
                            % (tuple(peaks.shape), self.num_keypoints))
         if not self._pinned and self.hist.device != peaks.device and peaks.device.type == "cuda":
             self.to(peaks.device)
+        if mask is not None:
+            from .masks import peaks_drop_masked
+            peaks, counts = peaks_drop_masked(peaks, counts, mask)
         ops.peaks_match(peaks, counts, labels, self.thresholds, self.hist, self.totals, bins=self.bins)
 
     def state(self):

@@ -599,6 +599,77 @@ def warp_affine_u8(img, plan, out_hw=None):
     return out
 
 
+def warp_mask_u8(mask, plan, fill=0, out_hw=None, lut=None, out=None):
+    """The ignore masks of a batch through its images' transforms (hkp_warp_mask_u8): mask
+    uint8 [B,Hs,Ws] and the batch's hkp.geometry.WarpPlan -> uint8 [B,H,W], one launch on the
+    current stream.  The plan's matrices and border are used, its interp is not: a mask is
+    always sampled nearest, by the image warp's own rule.  fill (0..255): the byte a pixel
+    outside the source gets under border="constant" (0: trained, 255: ignored for every
+    class).  lut: uint8 [B,256] on mask's device, the table each source byte goes through
+    (hkp.masks.flip_lut per flipped image; WarpPlan.apply_mask builds it), or None.  out: a
+    contiguous uint8 [B,H,W] tensor to write into (it may be an unaligned view)."""
+    from ._lib import HKP_WARP_BORDER_REFLECT101, HKP_WARP_MAX_DIM
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise HkpError("warp_mask_u8: fill is an integer in 0..255, got %r" % (fill,))
+    _need(mask, torch.uint8, "warp_mask_u8.mask", 3)
+    n, hs, ws = mask.shape
+    if n < 1 or not (1 <= hs <= HKP_WARP_MAX_DIM and 1 <= ws <= HKP_WARP_MAX_DIM):
+        raise HkpError("warp_mask_u8: need B >= 1 and H, W in 1..%d, got %s" % (HKP_WARP_MAX_DIM, tuple(mask.shape)))
+    if getattr(plan, "n", None) != n:
+        raise HkpError("warp_mask_u8: the plan holds %s transforms for a batch of %d" % (getattr(plan, "n", None), n))
+    h, w = plan.hw if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if not (1 <= h <= HKP_WARP_MAX_DIM and 1 <= w <= HKP_WARP_MAX_DIM):
+        raise HkpError("warp_mask_u8: out_hw %dx%d outside 1..%d" % (h, w, HKP_WARP_MAX_DIM))
+    if plan.border == HKP_WARP_BORDER_REFLECT101 and (hs < 2 or ws < 2):
+        raise HkpError("warp_mask_u8: reflect101 needs a source of at least 2x2, got %dx%d" % (hs, ws))
+    if lut is not None:
+        _need(lut, torch.uint8, "warp_mask_u8.lut", 2)
+        if tuple(lut.shape) != (n, 256) or lut.device != mask.device:
+            raise HkpError("warp_mask_u8: lut must be uint8 [%d,256] on %s, got %s on %s"
+                           % (n, mask.device, tuple(lut.shape), lut.device))
+    xf = plan.device_array(mask.device)
+    if out is None:
+        out = torch.empty((n, h, w), device=mask.device, dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "warp_mask_u8.out", 3)
+        if tuple(out.shape) != (n, h, w) or out.device != mask.device:
+            raise HkpError("warp_mask_u8: out must be uint8 [%d,%d,%d] on %s, got %s on %s"
+                           % (n, h, w, mask.device, tuple(out.shape), out.device))
+    call("hkp_warp_mask_u8", n, hs, ws, _ptr(mask), h, w, _ptr(out), plan.xforms, _ptr(xf), plan.border, fill,
+         _ptr(lut), _stream())
+    return out
+
+
+def mask_regions_u8(regions, H, W, out=None):
+    """Ignore masks from region records (hkp_mask_regions_u8): regions float32 [N,R,6] =
+    (kind, a, b, c, d, bits) on the device, 1 <= R <= 64, as hkp.masks.pack builds them ->
+    uint8 [N,H,W], every byte written in one launch on the current stream.  kind 1: the box
+    a <= x <= c, b <= y <= d; kind 2: the disc (x-a)^2 + (y-b)^2 <= c^2 (fp32); any other
+    kind: an empty slot.  A pixel gets the OR of the bits of the regions that hold it.
+    out: a uint8 [N,H,W] tensor to write into (it may be an unaligned view, as long as it is
+    contiguous)."""
+    from ._lib import HKP_MASK_MAX_DIM, HKP_MASK_MAX_REGIONS
+    H, W = int(H), int(W)
+    if not (1 <= H <= HKP_MASK_MAX_DIM and 1 <= W <= HKP_MASK_MAX_DIM):
+        raise HkpError("mask_regions_u8: H, W must be in 1..%d, got %dx%d" % (HKP_MASK_MAX_DIM, H, W))
+    if not isinstance(regions, torch.Tensor) or regions.dtype != torch.float32 or regions.dim() != 3 or \
+            regions.shape[2] != 6 or not 1 <= regions.shape[1] <= HKP_MASK_MAX_REGIONS or regions.shape[0] < 1:
+        raise HkpError("mask_regions_u8: regions must be float32 [N,R,6] with 1 <= R <= %d, got %s"
+                       % (HKP_MASK_MAX_REGIONS, "%s %s" % (regions.dtype, tuple(regions.shape))
+                          if isinstance(regions, torch.Tensor) else type(regions).__name__))
+    _need(regions, torch.float32, "mask_regions_u8.regions", 3)
+    n, r = regions.shape[:2]
+    if out is None:
+        out = torch.empty((n, H, W), device=regions.device, dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "mask_regions_u8.out", 3)
+        if tuple(out.shape) != (n, H, W) or out.device != regions.device:
+            raise HkpError("mask_regions_u8: out must be uint8 [%d,%d,%d] on %s, got %s on %s"
+                           % (n, H, W, regions.device, tuple(out.shape), out.device))
+    call("hkp_mask_regions_u8", n, r, H, W, _ptr(regions), _ptr(out), _stream())
+    return out
+
+
 def synth_cables_u8(plan, out=None):
     """Procedural cable scenes (csrc/synth.hip): the batch's hkp.synth.SynthPlan (one scene
     per image) → uint8 [B,H,W,3] BGR on the current device, one launch on the current
@@ -1565,13 +1636,38 @@ def _planes_choice(who, weights, topk, heat=None):
     return topk
 
 
-def _multi_loss_args(who, heat, pts, sigma, absent, planes=None):
+def _mask_choice(who, mask, heat=None):
+    """The ignore mask of a loss call, checked before any kernel is called and without
+    looking at a value: a contiguous uint8 tensor [N,H,W]; against heat, when that is given
+    as [N,K,H,W]: its shape and device, and K <= 8 (a mask byte holds 8 class bits)."""
+    from ._lib import MASK_MAX_K
+    if mask is None:
+        return
+    if not isinstance(mask, torch.Tensor):
+        raise HkpError("%s: mask must be a uint8 tensor [N,H,W], got %s" % (who, type(mask).__name__))
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise HkpError("%s: mask must be uint8 [N,H,W], got %s %s" % (who, mask.dtype, tuple(mask.shape)))
+    if not mask.is_contiguous():
+        raise HkpError("%s: mask must be contiguous" % who)
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        return
+    n, k, H, W = heat.shape
+    if k > MASK_MAX_K:
+        raise HkpError("%s: a mask holds %d class bits, heat has K = %d classes" % (who, MASK_MAX_K, k))
+    if tuple(mask.shape) != (n, H, W) or mask.device != heat.device:
+        raise HkpError("%s: mask must be uint8 [%d,%d,%d] on %s, got %s on %s"
+                       % (who, n, H, W, heat.device, tuple(mask.shape), mask.device))
+
+
+def _multi_loss_args(who, heat, pts, sigma, absent, planes=None, mask=None):
     """The checks heat_loss_multi and heat_loss_planes share, after _loss_choice and in this
-    order: the absent mode; with planes = (weights, topk), _planes_choice; heat, pts and
-    that they go together; sigma.  Returns topk as _planes_choice does (0 without planes)."""
+    order: the absent mode; with planes = (weights, topk), _planes_choice; the mask
+    (_mask_choice); heat, pts and that they go together; sigma.  Returns topk as
+    _planes_choice does (0 without planes)."""
     if absent not in ABSENT_MODES:
         raise HkpError("%s: unknown absent %r (known: %s)" % (who, absent, ", ".join(ABSENT_MODES)))
     topk = _planes_choice(who, planes[0], planes[1], heat) if planes is not None else 0
+    _mask_choice(who, mask, heat)
     _need(heat, torch.float32, who + ".heat", 4)
     _need_pts(pts, who + ".pts")
     if tuple(pts.shape[:2]) != tuple(heat.shape[:2]) or pts.device != heat.device:
@@ -1593,19 +1689,26 @@ def _uv_as_pts(heat, uv):
 
 
 def heat_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", want_grad=True, *, beta=2.0, norm="elements",
-              weights=None, topk=None):
+              weights=None, topk=None, mask=None):
     """fp64 BCE/MSE over [N,K,H,W] heatmaps → (loss 0-dim f64 tensor, dheat f32 or None).
     kind="qfl" (the quality focal loss of heat_loss_multi, with its beta and norm):
     from uv labels only, each taken as one present instance; a dense target raises.
     weights / topk (heat_loss_planes' plane weights and hard keypoint mining): from uv
-    labels only, likewise; the same two values are returned."""
+    labels only, likewise; the same two values are returned.
+    mask uint8 [N,H,W] (heat_loss_masked's per-pixel ignore mask of class bits, K <= 8): from
+    uv labels only, likewise; a dense target raises."""
     from ._lib import HKP_LOSS_BCE, HKP_LOSS_MSE, lib
-    if weights is not None or topk is not None:
+    if weights is not None or topk is not None or mask is not None:
         _loss_choice("heat_loss", kind, norm, beta)
         _planes_choice("heat_loss", weights, topk, heat)
+        _mask_choice("heat_loss", mask, heat)
         if target is not None:
-            raise HkpError("heat_loss: weights / topk recompute the target from uv; a dense target is not supported")
+            raise HkpError("heat_loss: weights / topk / mask recompute the target from uv; a dense target is not "
+                           "supported")
         pts = _uv_as_pts(heat, uv)
+        if mask is not None:
+            return heat_loss_masked(heat, pts, mask, sigma, kind, "zero", want_grad, beta=beta, norm=norm,
+                                    weights=weights, topk=topk)[:2]
         return heat_loss_planes(heat, pts, sigma, kind, "zero", want_grad, beta=beta, norm=norm, weights=weights,
                                 topk=topk)[:2]
     if kind == "qfl" or norm != "elements":
@@ -1649,7 +1752,8 @@ def heat_loss_planes(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=
     eligible (absent under "ignore", or not labelled).  plane_used: 1 for a counted plane.
     The divisor: norm="elements": H*W times the counted planes; "instances": max(1, the
     present slots of the counted planes).  With weights=None, topk=None the loss and dheat
-    are those of heat_loss_multi."""
+    are those of heat_loss_multi.  heat_loss_masked is this call with a per-pixel ignore
+    mask."""
     from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
                        HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
     beta = _loss_choice("heat_loss_planes", kind, norm, beta)
@@ -1668,8 +1772,44 @@ def heat_loss_planes(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=
     return loss, dheat, plane_loss, plane_used
 
 
+def heat_loss_masked(heat, pts, mask, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0,
+                     norm="elements", weights=None, topk=None):
+    """heat_loss_planes with a per-pixel ignore mask, one entry (hkp_heat_loss_masked) → (loss
+    0-dim f64, dheat f32 or None, plane_loss f64 [N,K], plane_used int32 [N,K], plane_pixels
+    int32 [N,K]); nothing is synchronised.  heat_loss_planes keeps its own signature and its
+    own entry; heat_loss_multi(mask=) and heat_loss(uv=, mask=) come here.
+    mask uint8 [N,H,W] on heat's device, in the frame of heat and pts (K <= 8): bit c of a
+    byte takes that pixel out for class c, 0xFF for every class.  A masked pixel adds
+    nothing, gets dheat +0, and its heat is never read into a result (NaN there changes no
+    output bit).  A plane's mean (plane_loss, and what topk ranks on, times the weight) runs
+    over its kept pixels; a plane without a kept pixel is not labelled, as with a weight of
+    0; norm="elements" divides by the kept pixels of the counted planes.  plane_pixels: the
+    kept pixels of every eligible plane, 0 for the others.  With an all-zero mask the first
+    four values have the bits of heat_loss_planes."""
+    from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
+                       HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    beta = _loss_choice("heat_loss_masked", kind, norm, beta)
+    if mask is None:
+        raise HkpError("heat_loss_masked: mask is required (heat_loss_planes is the call without one)")
+    topk = _multi_loss_args("heat_loss_masked", heat, pts, sigma, absent, (weights, topk), mask)
+    n, k, H, W = heat.shape
+    ws = torch.empty(lib().hkp_heat_loss_masked_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
+    loss = torch.empty((), device=heat.device, dtype=torch.float64)
+    dheat = torch.empty_like(heat) if want_grad else None
+    plane_loss = torch.empty((n, k), device=heat.device, dtype=torch.float64)
+    plane_used = torch.empty((n, k), device=heat.device, dtype=torch.int32)
+    plane_pixels = torch.empty((n, k), device=heat.device, dtype=torch.int32)
+    kd = {"bce": HKP_LOSS_BCE, "mse": HKP_LOSS_MSE, "qfl": HKP_LOSS_QFL}[kind]
+    call("hkp_heat_loss_masked", n, k, pts.shape[2], H, W, kd,
+         HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE,
+         HKP_NORM_ELEMENTS if norm == "elements" else HKP_NORM_INSTANCES, beta, topk, _ptr(heat), _ptr(pts),
+         _ptr(weights), _ptr(mask), float(sigma), _ptr(loss), _ptr(dheat), _ptr(plane_loss), _ptr(plane_used),
+         _ptr(plane_pixels), _ptr(ws), _stream())
+    return loss, dheat, plane_loss, plane_used, plane_pixels
+
+
 def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements",
-                    weights=None, topk=None):
+                    weights=None, topk=None, mask=None):
     """heat_loss against the multi-instance target of pts float32 [N,K,M,3] (u, v,
     flag), recomputed in registers → (loss 0-dim f64 tensor, dheat f32 or None).
     absent="zero": a plane without a present slot is trained against zeros;
@@ -1680,9 +1820,13 @@ def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=T
     norm="instances": the sum is divided by max(P, 1), P = the present slots of the
     batch (counted on the device), in place of the number of elements.
     The defaults reach hkp_heat_loss_multi; "qfl" or another norm hkp_heat_loss_multi_ex;
-    weights or topk: the first two values of heat_loss_planes."""
+    weights or topk: the first two values of heat_loss_planes; mask (uint8 [N,H,W] class
+    bits, K <= 8): the first two of heat_loss_masked."""
     from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
                        HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    if mask is not None:
+        return heat_loss_masked(heat, pts, mask, sigma, kind, absent, want_grad, beta=beta, norm=norm, weights=weights,
+                                topk=topk)[:2]
     if weights is not None or topk is not None:
         return heat_loss_planes(heat, pts, sigma, kind, absent, want_grad, beta=beta, norm=norm, weights=weights,
                                 topk=topk)[:2]

@@ -145,7 +145,10 @@ class Trainer:
         labelled), and per image only the topk planes with the largest weighted loss are
         counted.  The class weights are put on the device once.  With either key, or with
         weights passed to a step, trainer.plane_loss and trainer.plane_used are that step's
-        device tensors [B,K] (None otherwise); no host synchronisation is added.  Under data
+        device tensors [B,K] (None otherwise); no host synchronisation is added.  A step given
+        mask= (uint8 [B,H,W] class bits in the frame of the heatmaps, hkp.masks; point labels
+        only, K <= 8) leaves the masked pixels out of the loss (ops.heat_loss_masked) and
+        sets trainer.plane_pixels, the kept pixels per plane, next to the other two.  Under data
         parallelism each rank divides by its own divisor (its counted planes or their
         instances), as for "ignore" and "instances" above; the selection is per image, so it
         does not depend on how the batch is sharded.
@@ -208,7 +211,7 @@ class Trainer:
                 raise ValueError("class_weights must hold %d floats, got %d" % (model.num_keypoints, len(cw)))
         self._class_weights = cw              # the floats; the device tensor is built at the first step
         self.class_weights = None
-        self.plane_loss = self.plane_used = None
+        self.plane_loss = self.plane_used = self.plane_pixels = None
         self.sigma = sigma
         if absent not in ops.ABSENT_MODES:
             raise ValueError("absent must be one of %s, got %r" % (", ".join(ops.ABSENT_MODES), absent))
@@ -258,7 +261,8 @@ class Trainer:
             return None if self.class_weights is None else self.class_weights[None, :]
         return weights if self.class_weights is None else self.class_weights[None, :] * weights
 
-    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None):
+    def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None,
+                         mask=None):
         """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
         flag: the multi-instance target, absent planes per Trainer(absent=...)).
         weights: float32 [B,K] per-image plane weights (point labels only; see __init__).
@@ -269,13 +273,17 @@ class Trainer:
         if self.sync_bn:
             self.shard_check(x.shape[0], global_batch)
         m = self.model
-        planes = weights is not None or self._class_weights is not None or self.topk is not None
-        self.plane_loss = self.plane_used = None
+        planes = weights is not None or self._class_weights is not None or self.topk is not None or mask is not None
+        self.plane_loss = self.plane_used = self.plane_pixels = None
         if planes:                             # checked before the forward
             if target is not None or (pts is None) == (uv is None):
-                raise ops.HkpError("Trainer: class_weights, topk and weights need pts or uv labels alone; a dense "
-                                   "target is not supported")
+                raise ops.HkpError("Trainer: class_weights, topk, weights and mask need pts or uv labels alone; a "
+                                   "dense target is not supported")
             ops._planes_choice("Trainer", weights, self.topk)
+            ops._mask_choice("Trainer", mask)
+            if mask is not None and m.num_keypoints > 8:
+                raise ops.HkpError("Trainer: a mask holds 8 class bits, the model has K = %d classes"
+                                   % m.num_keypoints)
         self.tag_loss = None
         if self.tags is None:
             if gid is not None:
@@ -290,9 +298,14 @@ class Trainer:
             if w is not None:
                 w = w.expand(hm.shape[0], hm.shape[1]).contiguous()
             lab, absent = (pts, self.absent) if pts is not None else (ops._uv_as_pts(hm, uv), "zero")
-            loss, dheat, self.plane_loss, self.plane_used = ops.heat_loss_planes(
-                hm, lab, self.sigma, self.loss_kind, absent, want_grad=True, weights=w, topk=self.topk,
-                **self.loss_params)
+            if mask is not None:
+                loss, dheat, self.plane_loss, self.plane_used, self.plane_pixels = ops.heat_loss_masked(
+                    hm, lab, mask, self.sigma, self.loss_kind, absent, want_grad=True, weights=w, topk=self.topk,
+                    **self.loss_params)
+            else:
+                loss, dheat, self.plane_loss, self.plane_used = ops.heat_loss_planes(
+                    hm, lab, self.sigma, self.loss_kind, absent, want_grad=True, weights=w, topk=self.topk,
+                    **self.loss_params)
         elif pts is not None:
             if uv is not None or target is not None:
                 raise ops.HkpError("Trainer: pass pts alone, not with uv or target")
@@ -319,8 +332,11 @@ class Trainer:
                 p.grad = grads[p]
         return loss
 
-    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None):
-        loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid)
+    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None, mask=None):
+        if mask is None:                       # the call as it always was
+            loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid)
+        else:
+            loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid, mask=mask)
         self.opt.step()
         return loss
 

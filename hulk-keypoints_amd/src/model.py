@@ -119,14 +119,19 @@ class KeypointsGauss(nn.Module):
         return peaks, counts, group, tag
 
     @torch.no_grad()
-    def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None, tta=None):
+    def evaluate(self, x, labels, metrics, max_peaks=4, radius=1, threshold=0.0, policy=None, tta=None, mask=None):
         """predict_peaks, then one launch that matches the peaks to `labels` ([B,K,M,3]
         (u, v, flag) or [B,K,2], in input pixels, on the device) and adds the outcome
         into `metrics` (hkp.metrics.KeypointMetrics); no host synchronisation.
-        Returns the (peaks, counts) of predict_peaks.  tta: as for predict_peaks."""
+        Returns the (peaks, counts) of predict_peaks.  tta: as for predict_peaks.
+        mask uint8 [B,H,W] (hkp.masks, in input pixels): the peaks on ignored pixels are left
+        out of the match (KeypointMetrics.update(mask=)); what is returned is unfiltered."""
         peaks, counts = self.predict_peaks(x, max_peaks=max_peaks, radius=radius, threshold=threshold, policy=policy,
                                            tta=tta)
-        metrics.update(peaks, counts, labels)
+        if mask is None:
+            metrics.update(peaks, counts, labels)
+        else:
+            metrics.update(peaks, counts, labels, mask=mask)
         return peaks, counts
 
     @torch.no_grad()

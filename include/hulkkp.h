@@ -852,6 +852,44 @@ int hkp_heat_loss_planes(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, 
                          const float* pts, const float* weights, float sigma, double* loss, float* dheat,
                          double* plane_loss, int32_t* plane_used, void* workspace, hkp_stream_t stream);
 
+/* hkp_heat_loss_planes with a per-pixel ignore mask; not in the reference, and the entries
+ * above are unchanged.  mask uint8 [n][H][W], in the frame of the heatmaps and labels, one
+ * byte per pixel holding class bits: bit c set takes the pixel out for class c (0xFF: for
+ * every class), so k <= 8.  The k planes of an image read the same bytes.  Everything the
+ * planes entry defines holds, with these changes:
+ * keep:      keep(b,c,y,x) = !((mask[b][y][x] >> c) & 1); n_bc = the kept pixels of plane
+ *            (b, c), an exact integer counted on the device.
+ * eligible:  under the planes entry's rules AND n_bc > 0: a fully masked plane is "not
+ *            labelled", exactly as a weight of 0 is (dheat +0.0f, plane_loss -1.0, not in
+ *            the divisor).
+ * S[b][c]:   the fp64 sum of the unweighted per-element losses over the KEPT pixels, as
+ *            block partials in chunk order.  A masked pixel adds +0.0 and gets dheat +0.0f
+ *            by a select, not a product: whatever its heat holds (NaN included) changes no
+ *            output bit.  plane_loss = S / n_bc; plane_pixels = n_bc, 0 for a plane that is
+ *            not eligible.
+ * topk = T:  the eligible planes of an image are ranked by r = (double)w * (S / n_bc), the
+ *            weighted mean (what OHKM ranks on when planes differ in size); ties and NaN
+ *            as in the planes entry.
+ * divisor D: HKP_NORM_ELEMENTS: the sum of n_bc over the counted planes, exact, converted
+ *            to double (D = 0: loss 0, dheat 0); HKP_NORM_INSTANCES: max(P, 1), unchanged.
+ * values:    loss = (sum over the counted planes, in plane order, of (double)w * S) / D; on
+ *            kept pixels dheat = (float)(g * (double)w), g the fp64 gradient under D.  With
+ *            an all-zero mask every output has the bits of hkp_heat_loss_planes.
+ * launches:  a count pass over the mask (integers: any order), then the planes entry's
+ *            pre-kernel, pass, one-block finish and, with topk > 0, second pass.  No atomics
+ *            on floating values, no host synchronisation.
+ * mask is required (null: HKP_ERR_BAD_ARG; callers without a mask use the planes entry);
+ * it is read bytewise, or as 32-bit words where W % 4 == 0 and it is 4-byte aligned.
+ * plane_pixels [n][k] int32 is nullable like the other plane outputs.  k > 8 and every
+ * argument the planes entry refuses is HKP_ERR_BAD_ARG, and nothing is launched or written.
+ * workspace: hkp_heat_loss_masked_workspace(n, k, H, W) bytes. */
+int64_t hkp_heat_loss_masked_workspace(int32_t n, int32_t k, int32_t H, int32_t W);
+int hkp_heat_loss_masked(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W, int32_t loss_kind,
+                         int32_t absent_mode, int32_t norm_mode, float beta, int32_t topk, const float* heat,
+                         const float* pts, const float* weights, const uint8_t* mask, float sigma, double* loss,
+                         float* dheat, double* plane_loss, int32_t* plane_used, int32_t* plane_pixels,
+                         void* workspace, hkp_stream_t stream);
+
 /* Keypoint evaluation (not in the reference): the peaks and counts of
  * hkp_heat_peaks, peaks [n][k][p][3] (x, y, score) and counts [n][k], matched
  * plane by plane to the labels of hkp_heat_loss_multi, pts [n][k][m][3] (u, v,
@@ -1028,6 +1066,39 @@ typedef struct hkp_warp_xform {   /* 32 bytes */
 int hkp_warp_affine_u8(int32_t n, int32_t hs, int32_t ws, const uint8_t* img_in, int32_t h, int32_t w,
                        uint8_t* img_out, const hkp_warp_xform* xforms_host, const hkp_warp_xform* xforms,
                        int32_t interp, int32_t border, hkp_stream_t stream);
+
+/* The ignore masks of hkp_heat_loss_masked through the images' transforms: a one-channel
+ * warp of uint8 [n][hs][ws] into [n][h][w] with the records of hkp_warp_affine_u8 (their
+ * fill colours are not read) and exactly its HKP_WARP_NEAREST rule: Q16 coordinates,
+ * ix = (sx + 32768) >> 16, indices clamped into [-2, dim + 1] and then through the border
+ * rule, addresses from in-range indices only, in all three border modes.  The source byte
+ * goes through lut [n][256] (device, nullable: the identity) — how a flipped image
+ * exchanges the class bits of its flip pairs — and under HKP_WARP_BORDER_CONSTANT a pixel
+ * outside the source gets `fill` (0..255) as given, not through the table: 0 leaves the
+ * outside trained, 255 ignores it.  Rows leave as dwords when w % 4 == 0 and mask_out is
+ * 4-byte aligned, as bytes otherwise.  Limits and checks as hkp_warp_affine_u8. */
+int hkp_warp_mask_u8(int32_t n, int32_t hs, int32_t ws, const uint8_t* mask_in, int32_t h, int32_t w,
+                     uint8_t* mask_out, const hkp_warp_xform* xforms_host, const hkp_warp_xform* xforms,
+                     int32_t border, int32_t fill, const uint8_t* lut, hkp_stream_t stream);
+
+/* Ignore masks from region records: regions fp32 [n][r][6] = (kind, a, b, c, d, bits) in
+ * device memory, 1 <= r <= HKP_MASK_MAX_REGIONS, into out uint8 [n][H][W], every byte
+ * written in one launch (no memset).  Integer pixel coordinates are pixel centres; pixel
+ * (x, y) is inside
+ *   kind == 1 (box)   iff a <= x <= c and b <= y <= d
+ *   kind == 2 (disc)  iff (x-a)*(x-a) + (y-b)*(y-b) <= c*c, in fp32 with every product and
+ *                     sum rounded on its own (no contraction); d is not used
+ * and any other kind (NaN included) is an empty slot whose other fields are never read
+ * into the result.  A NaN bound is never inside.  bits is an integer 0..255 held in a
+ * float (anything else counts as 0).  out = the OR of the bits of the regions that hold
+ * the pixel.  H, W in [1, HKP_MASK_MAX_DIM], n in [1, 65535]; rows leave as dwords when
+ * W % 4 == 0 and out is 4-byte aligned, as bytes otherwise. */
+#define HKP_MASK_BOX 1
+#define HKP_MASK_DISC 2
+#define HKP_MASK_MAX_REGIONS 64
+#define HKP_MASK_MAX_DIM 4096
+int hkp_mask_regions_u8(int32_t n, int32_t r, int32_t H, int32_t W, const float* regions, uint8_t* out,
+                        hkp_stream_t stream);
 
 /* ------------------------------------------------- antialiased resize ---- */
 /* Batched antialiased resize of uint8 BGR images of ANY size (each image of the
