@@ -292,9 +292,13 @@ static int conv_geometry(const hkp_conv_desc* d, int* ho, int* wo) {
     HKP_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->c > 0 && d->k > 0 && d->r > 0 && d->s > 0,
                   "conv: non-positive size");
     HKP_CHECK_ARG(d->stride > 0 && d->dilation > 0 && d->pad >= 0, "conv: bad stride/dilation/pad");
-    *ho = (d->h + 2 * d->pad - d->dilation * (d->r - 1) - 1) / d->stride + 1;
-    *wo = (d->w + 2 * d->pad - d->dilation * (d->s - 1) - 1) / d->stride + 1;
-    HKP_CHECK_ARG(*ho > 0 && *wo > 0, "conv: empty output");
+    // a footprint larger than the padded image: the extent is negative, and with stride > 1
+    // the truncating division below would still make one output of it
+    const int eh = d->h + 2 * d->pad - d->dilation * (d->r - 1) - 1;
+    const int ew = d->w + 2 * d->pad - d->dilation * (d->s - 1) - 1;
+    HKP_CHECK_ARG(eh >= 0 && ew >= 0, "conv: empty output");
+    *ho = eh / d->stride + 1;
+    *wo = ew / d->stride + 1;
     return HKP_OK;
 }
 

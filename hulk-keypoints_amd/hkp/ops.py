@@ -72,7 +72,15 @@ def _need(t, dtype, name, ndim=None):
 
 
 def conv_out_hw(h, w, r, s, stride, pad, dil):
-    return ((h + 2 * pad - dil * (r - 1) - 1) // stride + 1, (w + 2 * pad - dil * (s - 1) - 1) // stride + 1)
+    """conv_geometry of csrc/conv_fwd.hip with its rejections: the wrappers size their
+    outputs from this before the library sees the descriptor."""
+    if stride <= 0 or dil <= 0 or pad < 0:
+        raise HkpError("conv: bad stride/dilation/pad")
+    # C division truncates, floor division does not: a footprint larger than the padded image is empty
+    eh, ew = h + 2 * pad - dil * (r - 1) - 1, w + 2 * pad - dil * (s - 1) - 1
+    if eh < 0 or ew < 0:
+        raise HkpError("conv: empty output")
+    return eh // stride + 1, ew // stride + 1
 
 
 def conv2d_fwd(x, w, stride=1, pad=0, dil=1, layout="nhwc", stats=True, out=None):
@@ -1192,6 +1200,17 @@ def gauss_target_multi(pts, H, W, sigma):
 # ------------------------------------------------------------------ backward
 
 
+def _shape4(shape, name):
+    """`shape` as a tuple of four positive ints (a descriptor is built from it unchecked)."""
+    try:
+        sh = tuple(shape)
+    except TypeError:
+        sh = None
+    if sh is None or len(sh) != 4 or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in sh):
+        raise HkpError("%s: expected four positive ints, got %r" % (name, shape))
+    return sh
+
+
 def _fwd_desc(x_shape, w_shape, stride, pad, dil, layout):
     if layout == "nhwc":
         n, h, wd, c = x_shape
@@ -1218,7 +1237,10 @@ def conv2d_bwd_data(dy, w_flip, x_shape, stride=1, pad=0, dil=1, add=None):
     """dL/dx (NHWC) of conv2d_fwd; ``add`` (same shape as x, nullable) is summed in."""
     _need(dy, torch.float32, "conv2d_bwd_data.dy", 4)
     _need(w_flip, torch.float32, "conv2d_bwd_data.w_flip", 4)
+    x_shape = _shape4(x_shape, "conv2d_bwd_data.x_shape")
     c, r, s, k = w_flip.shape
+    if c != x_shape[3]:
+        raise HkpError("conv2d_bwd_data: w_flip Cin %d != x_shape C %d" % (c, x_shape[3]))
     d = _fwd_desc(x_shape, (k, r, s, c), stride, pad, dil, "nhwc")
     ho, wo = conv_out_hw(x_shape[1], x_shape[2], r, s, stride, pad, dil)
     if tuple(dy.shape) != (x_shape[0], ho, wo, k):
@@ -1467,15 +1489,25 @@ def conv2d_bwd_filter(x, dy, w_shape, stride=1, pad=0, dil=1, layout="nhwc", out
     """dL/dw in the weight's own layout (KRSC, or OIHW for the NCHW stem)."""
     _need(x, torch.float32, "conv2d_bwd_filter.x", 4)
     _need(dy, torch.float32, "conv2d_bwd_filter.dy", 4)
-    d = _fwd_desc(tuple(x.shape), tuple(w_shape), stride, pad, dil, layout)
+    w_shape = _shape4(w_shape, "conv2d_bwd_filter.w_shape")
+    # the kernel writes k*r*s*C(x) floats: dw's Cin must be x's
+    cw, c = (w_shape[3], x.shape[3]) if layout == "nhwc" else (w_shape[1], x.shape[1])
+    if cw != c:
+        raise HkpError("conv2d_bwd_filter: w_shape Cin %d != input C %d" % (cw, c))
+    if out is not None:
+        _need(out, torch.float32, "conv2d_bwd_filter.dw")
+        if tuple(out.shape) != w_shape:
+            raise HkpError("conv2d_bwd_filter: out shape %s != %s" % (tuple(out.shape), w_shape))
+    elif accumulate:
+        raise HkpError("conv2d_bwd_filter: accumulate=True needs out= (there is nothing to add to)")
+    d = _fwd_desc(tuple(x.shape), w_shape, stride, pad, dil, layout)
     ho, wo = conv_out_hw(d.h, d.w, d.r, d.s, stride, pad, dil)
     if tuple(dy.shape) != (d.n, ho, wo, d.k):
         raise HkpError("conv2d_bwd_filter: dy shape %s != %s" % (tuple(dy.shape), (d.n, ho, wo, d.k)))
     from ._lib import lib
     nbytes = lib().hkp_conv_bwd_filter_workspace(ctypes.byref(d))
     ws = torch.empty(max(nbytes, 4) // 4, device=x.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
-    _need(dw, torch.float32, "conv2d_bwd_filter.dw")
+    dw = out if out is not None else torch.empty(w_shape, device=x.device, dtype=torch.float32)
     call("hkp_conv2d_bwd_filter", ctypes.byref(d), _ptr(x), _ptr(dy), _ptr(dw), int(bool(accumulate)), _ptr(ws),
          nbytes, _stream())
     return dw
