@@ -8,5 +8,6 @@ resample  antialiased resize of uint8 images of any size (axis tables, plans, la
 metrics   keypoint evaluation on the device (KeypointMetrics: PCK, precision, AP, mean error)
 tta       test-time augmentation: views of a batch and the merge of their low-res logits
 grouping  associative-embedding tags: default group labels and the pairing scores
+lines     line labels: segments from points and polylines, and LineMetrics for a centreline plane
 """
 from ._lib import HkpError, LIB_PATH, lib, version  # noqa: F401

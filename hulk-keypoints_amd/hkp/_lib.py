@@ -98,6 +98,7 @@ HKP_MASK_BOX, HKP_MASK_DISC = 1, 2
 HKP_MASK_MAX_REGIONS = 64
 HKP_MASK_MAX_DIM = 4096
 MASK_MAX_K = 8                     # class bits of a mask byte (hkp_heat_loss_masked)
+HKP_LINE_MAX_S = 128               # segment slots per plane of the line labels (hkp_line_target)
 
 
 class WarpXform(ctypes.Structure):
@@ -303,6 +304,8 @@ SIGNATURES = {
                                     _P]),
     "hkp_peaks_group": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), _F, _P, _P,
                                        _P, _I64, _P, _P, _P, _P]),
+    # line labels lines [n,k,s,5] (x0, y0, x1, y1, flag): target f64 and / or d2 f32, each nullable
+    "hkp_line_target": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

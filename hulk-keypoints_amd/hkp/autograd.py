@@ -114,7 +114,7 @@ class _HeatLossMaskedFn(torch.autograd.Function):
 
 
 def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, absent="zero", beta=2.0,
-                 norm="elements", weights=None, topk=None, return_planes=False, mask=None):
+                 norm="elements", weights=None, topk=None, return_planes=False, mask=None, lines=None):
     """mean BCE (default) or MSE between fp32 heatmaps and the fp64 Gaussian target
     (dense ``target`` or recomputed from ``uv``), returned as a 0-dim fp64 tensor.
     ``pts`` [N,K,M,3] (u, v, flag) in place of both: the multi-instance target
@@ -130,7 +130,31 @@ def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, ab
     plane_used [N,K] int32), the two extras detached.
     ``mask`` uint8 [N,H,W] (``uv`` or ``pts`` labels, K <= 8): the per-pixel ignore mask of
     ops.heat_loss_masked, bit c of a byte taking that pixel out for class c; with
-    ``return_planes`` a fourth value follows, plane_pixels [N,K] int32."""
+    ``return_planes`` a fourth value follows, plane_pixels [N,K] int32.
+    ``lines`` float32 [N,K,S,5] (hkp.lines), alone or with ``pts``: the dense target is
+    ops.line_target of the segments, the points of ``pts`` among them as zero-length
+    segments; "bce" / "mse", ``absent="zero"`` and ``norm="elements"`` only, and none of
+    ``weights``, ``topk``, ``return_planes``, ``mask``, ``uv`` or ``target``."""
+    if lines is not None:
+        from . import lines as L
+        if kind not in ("bce", "mse") or norm != "elements" or absent != "zero":
+            raise ops.HkpError("heatmap_loss: lines train through the dense target: kind 'bce' or 'mse', norm "
+                               "'elements' and absent 'zero', not %r / %r / %r" % (kind, norm, absent))
+        if weights is not None or topk is not None or return_planes or mask is not None:
+            raise ops.HkpError("heatmap_loss: weights, topk, return_planes and mask are not supported with lines")
+        if uv is not None or target is not None:
+            raise ops.HkpError("heatmap_loss: pass lines alone or with pts, not with uv or target")
+        if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+            raise ops.HkpError("heatmap_loss: heat must be a tensor [N,K,H,W]")
+        ops._lines_shape(lines, "heatmap_loss.lines")
+        if tuple(lines.shape[:2]) != tuple(heat.shape[:2]):
+            raise ops.HkpError("heatmap_loss: lines %s do not go with heat %s" % (tuple(lines.shape), tuple(heat.shape)))
+        ops._need_lines(lines, "heatmap_loss.lines")
+        if pts is not None:
+            ops._need_pts(pts, "heatmap_loss.pts")
+            lines = L.concat(L.from_points(pts), lines)
+        tgt, _ = ops.line_target(lines, heat.shape[2], heat.shape[3], sigma)
+        return _HeatLossFn.apply(heat, tgt, None, sigma, kind, beta, norm)
     if mask is not None:
         if target is not None or (pts is None) == (uv is None):
             raise ops.HkpError("heatmap_loss: a mask needs pts or uv labels alone; a dense target is not supported")

@@ -220,6 +220,34 @@ class WarpPlan:
                 out[b] = swap_pairs(out[b], self.flip_pairs)
         return torch.from_numpy(out) if is_t else out
 
+    def apply_lines(self, lines):
+        """Line labels through the batch's transforms: lines [n, K, S, 5] on the host
+        (x0, y0, x1, y1, flag; numpy or a CPU tensor, the same kind comes back, float32).
+        Both ends of the present slots (flag > 0) go through the forward matrix, as
+        apply_points' (u, v) do, and rows of `flip_pairs` are exchanged along K where the
+        image was flipped.  Nothing is clipped or dropped: the affine image of a segment
+        is the segment between the images of its ends, and the distance to it is defined
+        for every pixel.  Empty slots pass through as they are."""
+        is_t, a = host_lines(lines, self.n, "apply_lines")
+        out = np.array(a, dtype=np.float32, copy=True)
+        for b in range(self.n):
+            on = (out[b, :, :, 4] > 0)[..., None]
+            for e in (0, 2):
+                q = transform_uv(self.matrices[b], np.where(on, out[b, :, :, e:e + 2], 0.0))
+                out[b, :, :, e:e + 2] = np.where(on, q, out[b, :, :, e:e + 2])
+            if self.flipped[b]:
+                out[b] = swap_pairs(out[b], self.flip_pairs)
+        return torch.from_numpy(out) if is_t else out
+
+
+def host_lines(lines, n, who):
+    """(is a tensor, numpy view) of line labels [n, K, S, 5] on the host."""
+    is_t = isinstance(lines, torch.Tensor)
+    a = lines.detach().cpu().numpy() if is_t else np.asarray(lines)
+    if a.ndim != 4 or a.shape[0] != n or a.shape[3] != 5:
+        raise HkpError("%s: expected line labels [%d, K, S, 5], got %s" % (who, n, a.shape))
+    return is_t, a
+
 
 def host_points(pts, n, who):
     """(is a tensor, numpy view) of instance labels [n, K, M, 3] on the host."""

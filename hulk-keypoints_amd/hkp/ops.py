@@ -1197,6 +1197,55 @@ def gauss_target_multi(pts, H, W, sigma):
     return out
 
 
+def _lines_shape(lines, name):
+    """Line labels are a tensor [N,K,S,5], 1 <= S <= 128 (the shape alone: nothing is read)."""
+    from ._lib import HKP_LINE_MAX_S
+    if not isinstance(lines, torch.Tensor):
+        raise HkpError("%s: expected a tensor" % name)
+    if lines.dim() != 4 or lines.shape[3] != 5 or not 1 <= lines.shape[2] <= HKP_LINE_MAX_S or lines.shape[0] < 1 \
+            or lines.shape[1] < 1:
+        raise HkpError("%s: expected [N,K,S,5] with 1 <= S <= %d, got %s" % (name, HKP_LINE_MAX_S, tuple(lines.shape)))
+
+
+def _need_lines(lines, name):
+    """Line labels float32 [N,K,S,5] (x0, y0, x1, y1, flag), 1 <= S <= 128, on the GPU."""
+    _lines_shape(lines, name)
+    _need(lines, torch.float32, name, 4)
+
+
+def line_target(lines, H, W, sigma=8.0, want_target=True, want_d2=False, out=None, out_d2=None):
+    """lines float32 [N,K,S,5] (x0, y0, x1, y1, flag; flag > 0: present) → (target, d2):
+    d2 float32 [N,K,H,W], the squared distance to the nearest present segment (+inf for a
+    plane with none), and target float64 [N,K,H,W] = exp(-d2 / (2 sigma^2)) (0 for a plane
+    with none); whichever is not wanted is None.  A zero-length segment is a point.  out /
+    out_d2: preallocated outputs (contiguous, of the output's shape and dtype)."""
+    import math
+    if not (want_target or want_d2):
+        raise HkpError("line_target: neither target nor d2 is wanted")
+    if int(H) < 1 or int(W) < 1 or int(H) * int(W) > 1 << 30:
+        raise HkpError("line_target: bad size %sx%s (H, W >= 1, H*W <= 2^30)" % (H, W))
+    if not (float(sigma) > 0 and math.isfinite(float(sigma))):
+        raise HkpError("line_target: sigma %s must be finite and > 0" % (sigma,))
+    _need_lines(lines, "line_target.lines")
+    n, k, s, _ = lines.shape
+    H, W = int(H), int(W)
+    for o, want, dtype, name in ((out, want_target, torch.float64, "out"), (out_d2, want_d2, torch.float32, "out_d2")):
+        if o is None:
+            continue
+        if not want:
+            raise HkpError("line_target: %s given but not wanted" % name)
+        _need(o, dtype, "line_target." + name, 4)
+        if tuple(o.shape) != (n, k, H, W) or o.device != lines.device:
+            raise HkpError("line_target: %s %s on %s does not go with lines %s on %s, %dx%d"
+                           % (name, tuple(o.shape), o.device, tuple(lines.shape), lines.device, H, W))
+    if want_target and out is None:
+        out = torch.empty((n, k, H, W), device=lines.device, dtype=torch.float64)
+    if want_d2 and out_d2 is None:
+        out_d2 = torch.empty((n, k, H, W), device=lines.device, dtype=torch.float32)
+    call("hkp_line_target", n, k, s, H, W, float(sigma), _ptr(lines), _ptr(out), _ptr(out_d2), _stream())
+    return out, out_d2
+
+
 # ------------------------------------------------------------------ backward
 
 

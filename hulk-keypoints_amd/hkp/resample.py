@@ -281,6 +281,22 @@ class ResamplePlan:
         out[..., 2] = np.where(on & ~inside, 0.0, out[..., 2])
         return torch.from_numpy(out) if is_t else out
 
+    def apply_lines(self, lines):
+        """Line labels lines [n, K, S, 5] (x0, y0, x1, y1, flag) in source pixels (numpy or a
+        CPU tensor; the same kind comes back, float32) -> output pixels: both ends of the
+        present slots (flag > 0) through apply_points' map.  Nothing is clipped or dropped;
+        empty slots pass through as they are."""
+        from .geometry import host_lines
+        is_t, a = host_lines(lines, self.n, "apply_lines")
+        out = np.array(a, dtype=np.float32, copy=True)
+        gain, org = self._maps()
+        on = (out[..., 4] > 0)[..., None]
+        for e in (0, 2):
+            src = np.where(on, out[..., e:e + 2], 0.0).astype(np.float64)
+            q = ((src + 0.5) * gain[:, None] - 0.5 + org[:, None]).astype(np.float32)
+            out[..., e:e + 2] = np.where(on, q, out[..., e:e + 2])
+        return torch.from_numpy(out) if is_t else out
+
     def invert_uv(self, uv):
         """Predictions uv [n, K, 2] in output pixels -> the source image's pixels (not clipped)."""
         is_t, a = _host_uv(uv, self.n, "invert_uv")

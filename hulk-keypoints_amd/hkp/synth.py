@@ -21,9 +21,11 @@ Conventions
 import numpy as np
 import torch
 
-from ._lib import HKP_SYNTH_MAX_DIM, HKP_SYNTH_MAX_SEGS, MAX_INSTANCES, HkpError, SynthScene, SynthSeg
+from ._lib import (HKP_LINE_MAX_S, HKP_SYNTH_MAX_DIM, HKP_SYNTH_MAX_SEGS, MAX_INSTANCES, HkpError, SynthScene,
+                   SynthSeg)
 
 CLASSES = ("cap", "tail", "crossing", "blob")
+LINE_CLASSES = ("cable",)          # labelled by segments (hkp.lines), not by points
 DEFAULT_BACKGROUND = {"bg0": (40, 40, 40), "bg1": (96, 96, 96), "key": (0, 0), "cell_log2": 5}
 
 
@@ -134,6 +136,7 @@ class SynthPlan:
     """One batch of scenes for hkp_synth_cables_u8: `scenes` (ctypes SynthScene * n) and
     `segs` (ctypes SynthSeg * nsegs, the piece table in the kernel's fixed point), `hw`,
     `pts` (float32 [n, K, M, 3] labels, or None for a plan built from bare geometry),
+    `lines` (float32 [n, K, S, 5] line labels, or None when no class is a line class),
     `fallback` (bool [n]) and `descs` (the float64 scene descriptions, when sampled).
     device_arrays() uploads the records from pinned memory on the current stream; the plan
     keeps the pinned and the device copies alive, so keep it until the batch has been
@@ -142,7 +145,7 @@ class SynthPlan:
     pieces: per image a list of quantize_piece() dicts in drawing order; backgrounds: per
     image a dict with "bg0", "bg1" (B, G, R), "key" (two uint32) and "cell_log2" (4..12)."""
 
-    def __init__(self, hw, pieces, backgrounds, pts=None, fallback=None, descs=None):
+    def __init__(self, hw, pieces, backgrounds, pts=None, fallback=None, descs=None, lines=None):
         h, w = int(hw[0]), int(hw[1])
         if not (1 <= h <= HKP_SYNTH_MAX_DIM and 1 <= w <= HKP_SYNTH_MAX_DIM):
             raise HkpError("SynthPlan: hw %dx%d outside 1..%d" % (h, w, HKP_SYNTH_MAX_DIM))
@@ -171,6 +174,7 @@ class SynthPlan:
                     s.bgr[c] = p["bgr"][c]
                 off += 1
         self.pts = None if pts is None else np.ascontiguousarray(pts, dtype=np.float32)
+        self.lines = None if lines is None else np.ascontiguousarray(lines, dtype=np.float32)
         self.fallback = np.zeros(self.n, dtype=bool) if fallback is None else np.asarray(fallback, dtype=bool)
         self.descs = descs
         self._dev = {}
@@ -228,7 +232,9 @@ class CableScenes:
     classes     the label planes and their order, out of "cap" (the capped end of each
                 cable: vertex 0), "tail" (the other end), "crossing" (intersections of the
                 centrelines, a cable with itself or with another, neighbouring pieces
-                excluded) and "blob" (the disc centres); K = len(classes).
+                excluded) and "blob" (the disc centres), and out of LINE_CLASSES: "cable"
+                (the centrelines themselves, labelled by their pieces: line_labels; its
+                row of the point labels is empty); K = len(classes).
     cables      (lo, hi) cables per scene; ctrl: (lo, hi) control points per cable;
                 segments: straight pieces per cable; radius: (lo, hi) pixels.
     blobs       (lo, hi) filled discs per scene (distractors, and the easy class), of
@@ -267,8 +273,9 @@ class CableScenes:
                  margin=None):
         self.seed = int(seed)
         self.classes = tuple(classes)
-        if not self.classes or any(c not in CLASSES for c in self.classes) or len(set(self.classes)) != len(self.classes):
-            raise ValueError("classes must be distinct names out of %r, got %r" % (CLASSES, classes))
+        known = CLASSES + LINE_CLASSES
+        if not self.classes or any(c not in known for c in self.classes) or len(set(self.classes)) != len(self.classes):
+            raise ValueError("classes must be distinct names out of %r, got %r" % (known, classes))
         for name, r, lo in (("cables", cables, 1), ("ctrl", ctrl, 2), ("blobs", blobs, 0)):
             if len(r) != 2 or int(r[0]) != r[0] or int(r[1]) != r[1] or not lo <= r[0] <= r[1]:
                 raise ValueError("%s must be integers (lo, hi) with %d <= lo <= hi, got %r" % (name, lo, r))
@@ -281,6 +288,10 @@ class CableScenes:
             raise ValueError("instances must be 1..%d, got %r" % (MAX_INSTANCES, instances))
         if int(blobs[1]) + int(cables[1]) * (int(segments) + 1) > HKP_SYNTH_MAX_SEGS:
             raise ValueError("blobs + cables * (segments + 1) must not exceed %d pieces" % HKP_SYNTH_MAX_SEGS)
+        self.line_slots = int(cables[1]) * int(segments) if any(c in LINE_CLASSES for c in self.classes) else 0
+        if self.line_slots > HKP_LINE_MAX_S:
+            raise ValueError("a line class needs cables[1] * segments = %d segment slots (at most %d)"
+                             % (self.line_slots, HKP_LINE_MAX_S))
         self.cables, self.ctrl, self.blobs = tuple(map(int, cables)), tuple(map(int, ctrl)), tuple(map(int, blobs))
         self.segments, self.tries, self.instances = int(segments), int(tries), int(instances)
         self.radius, self.blob_radius = tuple(map(float, radius)), tuple(map(float, blob_radius))
@@ -411,12 +422,33 @@ class CableScenes:
         return ps
 
     def labels(self, d):
-        """float32 [K, M, 3] (u, v, flag) of scene description d; empty slots (0, 0, 0)."""
+        """float32 [K, M, 3] (u, v, flag) of scene description d; empty slots (0, 0, 0).  The
+        row of a line class is empty."""
         out = np.zeros((len(self.classes), self.instances, 3), dtype=np.float32)
         for k, c in enumerate(self.classes):
+            if c in LINE_CLASSES:
+                continue
             p = d["labels"][c]
             out[k, :len(p), :2] = p
             out[k, :len(p), 2] = 1.0
+        return out
+
+    def line_labels(self, d):
+        """float32 [K, S, 5] (x0, y0, x1, y1, flag) of scene description d, S = cables[1] *
+        segments: the "cable" row holds the cables' pieces, vertex pair by vertex pair, in
+        cable order then piece order; every other row, and the slots past the last piece,
+        are empty (0, 0, 0, 0, 0).  None when no class is a line class."""
+        if not self.line_slots:
+            return None
+        out = np.zeros((len(self.classes), self.line_slots, 5), dtype=np.float32)
+        k = self.classes.index("cable")
+        at = 0
+        for cab in d["cables"]:
+            v = cab["poly"]
+            out[k, at:at + len(v) - 1, 0:2] = v[:-1]
+            out[k, at:at + len(v) - 1, 2:4] = v[1:]
+            out[k, at:at + len(v) - 1, 4] = 1.0
+            at += len(v) - 1
         return out
 
     def plan(self, indices, epoch=0, hw=None):
@@ -428,7 +460,8 @@ class CableScenes:
             raise HkpError("CableScenes.plan: no indices")
         return SynthPlan(hw, [self.pieces(d) for d in descs], [d["background"] for d in descs],
                          pts=np.stack([self.labels(d) for d in descs]), fallback=[d["fallback"] for d in descs],
-                         descs=descs)
+                         descs=descs,
+                         lines=np.stack([self.line_labels(d) for d in descs]) if self.line_slots else None)
 
     def __call__(self, n, hw, index=None, epoch=None):
         """(img uint8 [n,H,W,3] on the current device, pts float32 [n,K,M,3] on it) of n

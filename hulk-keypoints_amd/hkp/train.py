@@ -261,10 +261,38 @@ class Trainer:
             return None if self.class_weights is None else self.class_weights[None, :]
         return weights if self.class_weights is None else self.class_weights[None, :] * weights
 
+    def _lines_choice(self, x, uv, target, pts, lines, planes):
+        """The checks of a step with line labels, before the forward; returns the labels the
+        target is made from: lines, with the points of pts in front as zero-length segments."""
+        from . import lines as L
+        who = "Trainer"
+        if self.loss_kind not in ("bce", "mse") or self.loss_params.get("norm", "elements") != "elements":
+            raise ops.HkpError("%s: lines train through the dense target: loss 'bce' or 'mse' with norm 'elements', "
+                               "not %r / %r" % (who, self.loss_kind, self.loss_params.get("norm", "elements")))
+        if self.absent != "zero":
+            raise ops.HkpError("%s: lines need absent='zero' (a plane without a present segment is a negative)" % who)
+        if planes:
+            raise ops.HkpError("%s: weights, class_weights, topk and mask are not supported with lines" % who)
+        if uv is not None or target is not None:
+            raise ops.HkpError("%s: pass lines alone or with pts, not with uv or target" % who)
+        ops._lines_shape(lines, who + ".lines")
+        nk = (x.shape[0], self.model.num_keypoints)
+        if tuple(lines.shape[:2]) != nk:
+            raise ops.HkpError("%s: lines %s do not go with %d images of %d classes" % ((who, tuple(lines.shape)) + nk))
+        ops._need_lines(lines, who + ".lines")
+        if pts is None:
+            return lines
+        ops._need_pts(pts, who + ".pts")
+        return L.concat(L.from_points(pts), lines)
+
     def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None,
-                         mask=None):
+                         mask=None, lines=None):
         """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
         flag: the multi-instance target, absent planes per Trainer(absent=...)).
+        lines: float32 [B,K,S,5] line labels (hkp.lines), alone or with pts: the heat target
+        is ops.line_target of the segments, the points of pts among them as zero-length
+        segments, and the loss is the dense ops.heat_loss against it.  "bce" / "mse" and
+        absent="zero" only; no weights, class_weights, topk or mask; tags read pts alone.
         weights: float32 [B,K] per-image plane weights (point labels only; see __init__).
         gid: int32 [B,K,M], Trainer(tags=...) only: the group of every slot of pts.
         global_batch (SyncBN): the job's batch size — the same on every rank, x
@@ -290,10 +318,14 @@ class Trainer:
                 raise ops.HkpError("Trainer: gid goes with Trainer(tags=...)")
         elif pts is None or uv is not None or target is not None:      # checked before the forward
             raise ops.HkpError("Trainer: tags need pts labels alone; uv and a dense target carry no groups")
+        lab_lines = None if lines is None else self._lines_choice(x, uv, target, pts, lines, planes)
         trace = net.Trace(self.policy)
         kw = {} if self.tags is None else {"tags": True}           # tags off: the call as it always was
         hm, _, low = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace, **kw)
-        if planes:
+        if lab_lines is not None:
+            tgt, _ = ops.line_target(lab_lines, hm.shape[2], hm.shape[3], self.sigma)
+            loss, dheat = ops.heat_loss(hm, tgt, None, self.sigma, self.loss_kind, want_grad=True)
+        elif planes:
             w = self._plane_weights(weights, hm.device)
             if w is not None:
                 w = w.expand(hm.shape[0], hm.shape[1]).contiguous()
@@ -332,8 +364,12 @@ class Trainer:
                 p.grad = grads[p]
         return loss
 
-    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None, mask=None):
-        if mask is None:                       # the call as it always was
+    def step(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None, mask=None,
+             lines=None):
+        if lines is not None:
+            loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid, mask=mask,
+                                         lines=lines)
+        elif mask is None:                     # the call as it always was
             loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid)
         else:
             loss = self.forward_backward(x, uv, target, global_batch, pts=pts, weights=weights, gid=gid, mask=mask)

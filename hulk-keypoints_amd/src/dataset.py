@@ -238,7 +238,11 @@ class SynthDataset(Dataset):
     idiom of train.py (keep num_workers=0): one image rendered by a B = 1 launch, through
     `transform`; items are (img, pts) with return_uv=True, else (img, gaussians) from
     hkp_gauss_target_multi.  raw(i) returns (uint8 [H,W,3] BGR on the host, fp32 [K,M,3]
-    on the device)."""
+    on the device).
+    When the scenes have a line class (hkp.synth.LINE_CLASSES), and only then, the line
+    labels lines [K,S,5] (hkp.lines) ride along: raw(i) and, with return_uv=True, the items
+    are (img, pts, lines); with return_uv=False the gaussians are ops.line_target of the
+    points and the segments together."""
 
     def __init__(self, scenes, length, hw, epoch=0, fixed=False, rank=0, world=1, transform=transform, return_uv=True,
                  device="cuda", gauss_sigma=8):
@@ -274,10 +278,21 @@ class SynthDataset(Dataset):
         plan = self.plan([index])
         with torch.cuda.device(self.device):
             img = ops.synth_cables_u8(plan)[0].cpu().numpy()
+        if plan.lines is not None:
+            return img, torch.from_numpy(plan.pts[0]).to(self.device), torch.from_numpy(plan.lines[0]).to(self.device)
         return img, torch.from_numpy(plan.pts[0]).to(self.device)
 
     def __getitem__(self, index):
-        img, pts = self.raw(index)
+        got = self.raw(index)
+        if len(got) == 3:                      # scenes with a line class
+            from hkp import lines as L
+            img, pts, lines = got
+            img = self.transform(img)
+            if self.return_uv:
+                return img, pts, lines
+            lab = L.concat(L.from_points(pts.unsqueeze(0)), lines.unsqueeze(0))
+            return img, ops.line_target(lab, self.img_height, self.img_width, self.gauss_sigma)[0][0]
+        img, pts = got
         img = self.transform(img)
         if self.return_uv:
             return img, pts
@@ -443,7 +458,9 @@ class DeviceBatches:
     (scenes, this epoch — the dataset's own with fixed=True —, its scene indices) and its
     pts uploaded from the plan;
     `geometric` and `augment` then apply exactly as for decoded batches, under the scene
-    indices.  `resize` and decode="device" raise for it."""
+    indices.  `resize` and decode="device" raise for it.  Scenes with a line class yield
+    (img, pts, lines fp32 [B,K,S,5]) for Trainer.step(img, pts=pts, lines=lines); `geometric`
+    moves the lines with plan.apply_lines (nothing is clipped or dropped)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, drop_last=False, device="cuda", workers=0,
                  prefetch=4, decode="host", augment=None, geometric=None, resize=None):
@@ -576,11 +593,14 @@ class DeviceBatches:
                 plan = ds.plan(items, epoch)
                 img = ops.synth_cables_u8(plan)
                 pts = torch.from_numpy(plan.pts)
+                lines = None if plan.lines is None else torch.from_numpy(plan.lines)
                 buf = plan                     # the plan's pinned records live as long as the batch
                 if self.geometric is not None:
                     gplan = self.geometric.plan(idx, epoch, uvs=pts, hw=(img.shape[1], img.shape[2]))
                     img = ops.warp_affine_u8(img, gplan)
                     pts = gplan.apply_points(pts)
+                    if lines is not None:
+                        lines = gplan.apply_lines(lines)
                     buf = (buf, gplan)
                 if self.augment is not None:
                     aplan = self.augment.plan(idx, epoch)
@@ -588,16 +608,24 @@ class DeviceBatches:
                     buf = (buf, aplan)
                 pts = pts.pin_memory()
                 ptsd = pts.to(self.device, non_blocking=True)
+                linesd = None
+                if lines is not None:           # scenes with a line class
+                    lines = lines.pin_memory()
+                    linesd = lines.to(self.device, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)
-            return img, ptsd, ev, (buf, pts)
+            return img, ptsd, linesd, ev, (buf, pts, lines)
 
         nxt = stage(batches[0]) if batches else None
         for bi in range(len(batches)):
-            img, pts, ev, buf = nxt
+            img, pts, lines, ev, buf = nxt
             nxt = stage(batches[bi + 1]) if bi + 1 < len(batches) else None
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             img.record_stream(cur)
             pts.record_stream(cur)
-            yield img, pts
+            if lines is None:
+                yield img, pts
+            else:
+                lines.record_stream(cur)
+                yield img, pts, lines

@@ -33,7 +33,11 @@ sets are procedural cable scenes rendered on the GPU (hkp.synth.CableScenes thro
 src.dataset.SynthDataset) with instance labels [K,M,3]; the train set draws new scenes every
 epoch, the test set is fixed and comes from seed + 1.  NUM_KEYPOINTS must equal the number
 of classes; GEOMETRIC_AUGMENTATION and RESIZE do not go with it here (DeviceBatches takes
-geometric= for a SynthDataset).
+geometric= for a SynthDataset).  When config.SYNTH["classes"] holds a line class
+(hkp.synth.LINE_CLASSES: "cable", labelled by its centreline's pieces), both sets are built with
+return_uv=False: the items carry the dense target of hkp_line_target over points and segments
+together, the reference's dense target -> BCE path, which _loss takes as it stands.  EVAL and
+TAGS need point labels and raise at start-up with such scenes.
 
 With config.LOSS = "qfl" (default "bce": nothing changes) the train and the test loop take
 the quality focal loss of hkp_heat_loss_multi_ex, with config.LOSS_PARAMS's beta and norm;
@@ -333,9 +337,16 @@ def main(dataset_dir="", output_dir="checkpoints", workers=0):
         if geometric is not None or resize is not None:
             raise ValueError("config.SYNTH does not go with GEOMETRIC_AUGMENTATION or RESIZE in train.py")
         train_scenes, test_scenes, n_train, n_test = synth_from_config(SYNTH, NUM_KEYPOINTS)
+        dense = {}
+        if train_scenes.line_slots:                 # a line class: the items carry the dense target
+            if EVAL is not None or TAGS is not None:
+                raise ValueError("config.SYNTH['classes'] %r holds a line class: its items are dense targets, and "
+                                 "config.EVAL and config.TAGS need point labels" % (train_scenes.classes,))
+            dense = {"return_uv": False}
         train_dataset = SynthDataset(train_scenes, n_train, (IMG_HEIGHT, IMG_WIDTH), transform=train_transform,
-                                     gauss_sigma=GAUSS_SIGMA)
-        test_dataset = SynthDataset(test_scenes, n_test, (IMG_HEIGHT, IMG_WIDTH), fixed=True, gauss_sigma=GAUSS_SIGMA)
+                                     gauss_sigma=GAUSS_SIGMA, **dense)
+        test_dataset = SynthDataset(test_scenes, n_test, (IMG_HEIGHT, IMG_WIDTH), fixed=True, gauss_sigma=GAUSS_SIGMA,
+                                    **dense)
     else:
         train_dataset = KeypointsDataset("data/%s/train/images" % dataset_dir,
                                          "data/%s/train/keypoints" % dataset_dir, NUM_KEYPOINTS, IMG_HEIGHT,

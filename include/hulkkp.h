@@ -1380,6 +1380,47 @@ int hkp_peaks_group(int32_t n, int32_t k, int32_t p, int32_t h, int32_t w, int32
                     const float* tags, int64_t batch_stride, float* tag, int32_t* group, int32_t* ngroups,
                     hkp_stream_t stream);
 
+/* ============================ line labels: the centreline target ================ */
+/* A heatmap class trained against a polyline (a cable's centreline) instead of
+ * points: the Gaussian of the distance to the nearest segment, and that distance
+ * (csrc/lines.hip; tests/_lines_ref.py restates it in numpy).  The reference has no
+ * counterpart; its path from here on is dense target -> BCE (hkp_heat_loss).
+ *
+ * lines float32 [n][k][s][5], last axis (x0, y0, x1, y1, flag), 1 <= s <= HKP_LINE_MAX_S.
+ *   frame   that of pts: x is the column, y the row, integers are pixel centres;
+ *           coordinates may lie outside the picture.
+ *   flag    > 0 marks a present segment; anything else (NaN included) is an empty
+ *           slot whose coordinates are never read into a result.  Slots need not be
+ *           packed.  Present coordinates are finite with |.| <= 32768: the caller's
+ *           duty, not checked (there is no host read).
+ * Per plane and pixel (x, y), all in fp32 without contraction or fused multiply-add,
+ * over the present slots in slot order:
+ *    dx = x1 - x0;  dy = y1 - y0;  l2 = dx*dx + dy*dy;              (per segment, once)
+ *    inv = 1.0f / l2                                (IEEE division; only when l2 > 0)
+ *    px = (float)x - x0;  py = (float)y - y0;
+ *    t  = l2 > 0 ? fminf(fmaxf((px*dx + py*dy) * inv, 0.f), 1.f) : 0.f
+ *                                   (fmaxf / fminf's NaN rule: a NaN product gives t = 0)
+ *    cx = px - t*dx;  cy = py - t*dy;
+ *    d2 = fminf(d2, cx*cx + cy*cy)                                  (starts at +inf)
+ * Outputs, each nullable, at least one given:
+ *    d2     float32 [n][k][H][W]  the minimum above; +inf for a plane without a
+ *                                 present slot
+ *    target float64 [n][k][H][W]  (double)expf(-d2 / den), den as in hkp_gauss_target,
+ *                                 (float)(2.0 * (double)sigma * (double)sigma); +0.0
+ *                                 for a plane without a present slot
+ * A zero-length segment gives t = 0, cx = px, cy = py: hkp_gauss_target's
+ * (x-u)^2 + (y-v)^2 in its operation order, so a plane of points has the bits of
+ * hkp_gauss_target_multi at m = 1 (and at m > 1 as far as expf is monotone).
+ * One launch, no atomics, no workspace, no host synchronisation: the same input gives
+ * the same bits.  The kernel drops, per tile, the segments that cannot be nearest to
+ * any of its pixels; the outputs are the bits of the definition above regardless.
+ * n, k, H, W >= 1, 1 <= s <= HKP_LINE_MAX_S, H*W <= 2^30, sigma finite and > 0 (checked
+ * even when target is NULL, where it is not read), lines and at least one output
+ * non-null; anything else is HKP_ERR_BAD_ARG and nothing is launched or written. */
+#define HKP_LINE_MAX_S 128
+int hkp_line_target(int32_t n, int32_t k, int32_t s, int32_t H, int32_t W, float sigma,
+                    const float* lines, double* target, float* d2, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
