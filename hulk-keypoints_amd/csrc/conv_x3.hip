@@ -1,6 +1,7 @@
 // f16x3 implicit-GEMM convolution (the main-path conv arithmetic), deep-pipelined:
 // forward, stride-1 backward-data (the same kernel on the gradient with flipped
-// weights), backward-filter, and the 7x7/s2 stem.
+// weights) and the 7x7/s2 stem.  Backward-filter: wgrad_x3.hip; the operand
+// packers: pack_x3.hip; what both share with this file: x3_dev.h.
 //
 // f16x3 arithmetic: every operand v is split as hi = f16(v), lo = f16(v - hi) and
 //     v_a * v_b ≈ hi_a*hi_b + hi_a*lo_b + lo_a*hi_b
@@ -58,194 +59,9 @@
 
 #include "common.h"
 #include "x3_plan.h"
+#include "x3_dev.h"
 
 namespace hkp {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __attribute__((aligned(256))) uint4 g_x3_zero_line[8];   // 128 B of zeros (static, zero-initialised)
-// 128 B of all-ones bytes: a NaN in fp32 and in fp16.  The halo body's
-// out-of-image lines when it applies the input's BN itself (X3Args::in_ss):
-// relu(NaN * s + t) = 0 for any s, t, as a zero-padded post-ReLU input.
-__device__ __attribute__((aligned(256))) uint4 g_x3_nan_line[8] = {
-    {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u},
-    {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u}, {~0u, ~0u, ~0u, ~0u}};
-
-struct X3Args {
-    const _Float16* xs;
-    const _Float16* ws;
-    const float* wscale;   // per output channel inverse weight scale [K] (nullable: 1)
-    float* y;              // fp32 output, or
-    _Float16* y16 = nullptr;   // fp16 output (plain-fp16 path, autocast semantics)
-    float* part;
-    const unsigned* amax;  // max|input| bits: the input was scaled by pow2_scale_for(amax) (dgrad)
-    const float* add;      // addend of the output (dgrad: the residual-branch gradient), nullable
-    int N, H, W, C, K, R, S, stride, pad, dil, Ho, Wo;
-    int M, nks, cch, n_tiles, RS;
-    long plane;            // STEM: halves between the hi and lo image planes
-    // phase output (strided dgrad): output pixel (n, ho, wo) of this launch is
-    // written at (n, ho*ost + oy, wo*ost + ox) of an [N][OH][OW][K] tensor; ost = 0: dense
-    int ost = 0, OH = 0, OW = 0, oy = 0, ox = 0;
-    // stream-K (sk_units > 0): the grid's blocks split tiles x K-steps into equal
-    // unit ranges; a tile split between blocks is summed by its last-arriving
-    // block from per-segment fp32 slabs (sk_ws) — sk_cnt[tile] arrival counters,
-    // zero on entry and left zero
-    int mt0 = 0;           // m-tile offset of this launch (the split-K tail launch of conv_x3_tail_kernel)
-    // region base (a region of conv_x3_a3_mix_kernel; 0 everywhere else): the tiles'
-    // rows start at m_base — tile mt is rows m_base + (mt + mt0) * BM — and their BN
-    // partial tiles at part_base
-    int m_base = 0, part_base = 0;
-    // mixed-height launch (conv_x3_a3_mix_kernel): blocks [0, mix_b1) are the 256-row
-    // region's tiles, [mix_b1, mix_b2) the 192-row region's (from row mix_m1, partial
-    // tile mix_p1), the rest the 160-row region's (mix_m2, mix_p2); a region may be empty
-    int mix_b1 = 0, mix_b2 = 0, mix_m1 = 0, mix_m2 = 0, mix_p1 = 0, mix_p2 = 0;
-    long sk_units = 0;
-    float* sk_ws = nullptr;
-    unsigned* sk_cnt = nullptr;
-    // the stream-K grid sk_combine works in when it is not the launch's grid: its
-    // block count (0: gridDim.x) and this block's index in it (after the XCD remap)
-    int sk_grid = 0, sk_b = 0;
-    // split-K tail (every group's range inside one m-tile): one slab per group
-    // (slot gg * n_tiles + nt) instead of the stream-K grid's two
-    int sk_one = 0;
-    // A3 launches with the split-K tail appended (conv_x3_a3_kernel): blocks
-    // [0, main_blocks) run the full rounds' tiles, the rest the tail's segments —
-    // tail_groups groups of n_tiles blocks over tail_units (m-tile, K-step) units
-    // from m-tile tail_mt0 (the one-launch form of conv_x3_tail_kernel)
-    int main_blocks = 0, tail_groups = 0, tail_mt0 = 0;
-    long tail_units = 0;
-    unsigned long long* stamps = nullptr;   // debug: per-block phase clocks (hkp_debug_x3_stamps)
-    // first-round stagger: blocks b < stagger_blocks with (b >> 3) & 1 (half the CUs
-    // of every XCD) wait stagger_ticks (s_memrealtime, 100 MHz) before starting, so
-    // the CUs' epilogues (HBM-bound stores) do not all coincide with each other
-    int stagger_blocks = 0, stagger_ticks = 0;
-    // fused BN apply of the output (P 1, hkp_conv2d_fwd_f16_bn): out = [relu](y*s + t
-    // [+ res | + res*rs + rt]) on the fp16-rounded y, bn_apply_f16's arithmetic
-    const float* ep_ss = nullptr;          // [2K] scale | shift
-    const _Float16* ep_res = nullptr;      // residual [M][K] fp16, nullable
-    const float* ep_rss = nullptr;         // residual scale | shift [2K], nullable (raw residual)
-    int ep_relu = 0;
-    // fused input BN (the halo body, inference): xs is the producer conv's raw
-    // NHWC output (fp32 for P 3, fp16 for P 1) and the A operand is
-    // relu(x * s + t) — bn_apply's arithmetic — split into hi | lo (P 3) in LDS
-    const float* in_ss = nullptr;          // [2C] scale | shift
-    // epilogue output stores (A/B: hkp_debug_x3_store): 0 each site's own flavour,
-    // 1 plain, 2 nontemporal, 3 sc1 (written through, not kept in the XCD's L2), 4 sc0 sc1
-    int st_kind = 0;
-    // A/B (hkp_debug_x3_prio): static wave priority in the A3 K loop — 0 none, 1
-    // s_setprio 1 on waves 4-7 (the second wave on each SIMD), 2 on waves 0-3
-    int prio = 0;
-#ifdef HKP_AB_KNOBS
-    // A/B probe (hkp_debug_x3_a_wrap): the one-tile and DUO bodies read the A operand of row
-    // m from row m % a_wrap (0: off) — wrong outputs, but an L2-resident A stream —
-    // to time a conv's K loop without the activation lines' HBM / MALL latency
-    int a_wrap = 0;
-#endif
-};
-
-// One 16-B epilogue output store of flavour `kind` (X3Args::st_kind); dflt: the
-// site's own flavour for kind 0 (1 plain, 2 nontemporal).  Measured per site
-// (tools/conv_ab.py / infer_ab.py --stores, profiles/r05_store_ab.log): the fp32
-// ring-body tile nontemporal (C2 +0.8 %); the plain-fp16 tile plain (C4: nt -0.4 %,
-// sc1 -1.6 % end to end, although nt wins 4-7 % per conv in isolation), the fused
-// BN epilogue nontemporal
-typedef unsigned x3u32x4 __attribute__((ext_vector_type(4)));
-template <typename V>
-__device__ __forceinline__ void x3_st16(V* p, const V& val, int kind, int dflt) {
-    static_assert(sizeof(V) == 16, "16-B store");
-    x3u32x4 v;
-    __builtin_memcpy(&v, &val, 16);
-    x3u32x4* q = (x3u32x4*)p;
-    const int k = kind ? kind : dflt;
-    if (k == 2) {
-        __builtin_nontemporal_store(v, q);
-    } else if (k == 3) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(q), "v"(v) : "memory");
-    } else if (k == 4) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(q), "v"(v) : "memory");
-    } else {
-        *q = v;
-    }
-}
-
-// debug phase stamps (s_memrealtime, 100 MHz) of one-tile conv blocks: slot k of
-// block b at stamps[b * 8 + k]; written by lane 0 of wave 0
-__device__ __forceinline__ void x3_stamp(const X3Args& a, int k) {
-    if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
-}
-// debug: where the block runs — slot 6: HW_REG_HW_ID (CU / SH / SE ids), slot 7: HW_REG_XCC_ID
-__device__ __forceinline__ void x3_stamp_where(const X3Args& a) {
-    if (a.stamps && threadIdx.x == 0) {
-        a.stamps[blockIdx.x * 8 + 6] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-        a.stamps[blockIdx.x * 8 + 7] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);
-    }
-}
-
-// 2^e putting max|x| in [2^13, 2^14) (1 for 0 / non-finite): exact scaling
-__device__ __forceinline__ float pow2_scale_of(float m) {
-    if (!(m > 0.f) || !(m < INFINITY)) return 1.f;
-    int e;
-    frexpf(m, &e);
-    e = 14 - e;
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    return ldexpf(1.f, e);
-}
-
-// raw workgroup barrier (no vmcnt(0) drain: LDS-DMA stays in flight across it) +
-// compiler fence so no LDS access is moved across it
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// workgroup barrier for LDS traffic only: this wave's LDS ops retired, no
-// vmcnt(0) — __syncthreads() would also wait for every global store of the
-// epilogue to complete (~2-5 us under the other CUs' output writes)
-__device__ __forceinline__ void lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    lds_barrier();
-}
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// LDS-DMA through a raw buffer resource: address = base + soffset + voffset; a
-// voffset >= num_records (soffset is not range-checked) loads zeros — the
-// out-of-image taps and the rows past M cost one v_cndmask instead of a 64-bit
-// address select, and the per-K-step tap offset rides in the scalar soffset.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-extern "C" __device__ void hkp_raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size,
-                                                   int voffset, int soffset, int offset,
-                                                   int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ i32x4 buffer_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32) & 0xFFFF);   // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);                          // num_records
-    r[3] = 0x00020000;                                                            // gfx9 raw-buffer config
-    return r;
-}
-__device__ __forceinline__ void blds16(i32x4 rsrc, unsigned voff, unsigned soff, char* lds_wave_base) {
-    hkp_raw_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
-
-// schedule NM MFMAs and NR ds_reads of one basic block as evenly spread
-// groups: MFMA first, then one read after every NM/NR MFMAs
-template <int NM, int NR>
-__device__ __forceinline__ void interleave() {
-    constexpr int per = NM >= NR ? NM / NR : 1;
-    constexpr int nr = NM >= NR ? NR : NM;          // reads paired with MFMA groups
-#pragma unroll
-    for (int k = 0; k < nr; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, per, 0);   // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // ds_read
-    }
-    if constexpr (NR > nr) __builtin_amdgcn_sched_group_barrier(0x100, NR - nr, 0);
-    if constexpr (NM > per * nr) __builtin_amdgcn_sched_group_barrier(0x008, NM - per * nr, 0);
-}
 
 // LDS ring depth of a conv_x3 tile config (32-channel / 128-B stages): 256x256
 // tiles 2 (B fragments refilled per column instead), two blocks per CU (PAIR:
@@ -1660,1750 +1476,15 @@ __global__ __launch_bounds__(512, 1) void conv_x3_tail_kernel(X3Args a) {
     conv_x3_tile<BN, false, false, 16, P>(a, smem, mt * NT + nt, ks, ke - ks, true);
 }
 
-// ---------------------------------------------------------------------------
-// Halo-tile body (conv_x3_halo_kernel<P>) for stride-1 3x3 convs with pad =
-// dilation = 1 whose output tiles exactly into 8 x 32 pixel patches (Ho % 8 ==
-// 0, Wo % 32 == 0): layer1 of every R-net here (64 channels at 120x160 in
-// C2-C4, 240x320 in C5), forward and stride-1 dgrad.  The one-tile kernels
-// stage, per K-step, a tap-shifted 256-row A window — every input line is
-// fetched from L2 nine times, and at Cin = 64 (2 channel groups x 9 taps) the
-// 256x64 tile is bound by that operand stream, not by its MFMAs.  Here a tile is
-// an 8 x 32 patch of one image: per channel group its (8+2) x (32+2) = 340
-// input lines are staged ONCE by LDS-DMA into a halo image and the nine taps
-// read their fragments from it (tile row m = pixel (m/32, m%32) reads halo line
-// (m/32 + r) * 34 + m%32 + s for tap (r, s)); only the 64-row weight stage
-// streams per K-step (a 3-slot ring).  A tile moves 2 x 42.5 + 18 x 8 = 229 KB
-// from L2 instead of 18 x 40 = 720 KB.  Lines past the image are zero lines.
-// The 16-B chunk swizzle (halo_swz: line & 6) is keyed on the halo line, so any
-// 16 consecutive lines a fragment read touches are conflict-free, as in the ring.
-// Two blocks per CU (72 KB each): one block's halo reload / epilogue overlaps the
-// other's MFMAs.  256 x 64 tile, 8 waves 4 x 2 (wave tile 64 x 32), 16x16x32
-// MFMAs; epilogue = the one-tile kernels' (BN tile partials from the
-// accumulators, LDS-staged 16-B row chunks), rows remapped to the patch pixels.
-constexpr int HALO_LW = HALO_PW + 2, HALO_NL = (HALO_PH + 2) * HALO_LW;   // 340 lines (HALO_PH x HALO_PW patches: x3_plan.h)
-constexpr int HALO_GA = 6;                                   // halo DMA instructions per wave (48 x 8 lines >= 340)
-constexpr int HALO_ABYTES = 8 * HALO_GA * 8 * 128;           // 48 KiB: halo image (+ 44 dummy lines)
-constexpr int HALO_NSTB = 3, HALO_BSTAGE = 64 * 128;         // weight ring: 3 x 8 KiB
-constexpr int HALO_LDS = HALO_ABYTES + HALO_NSTB * HALO_BSTAGE;
+}  // namespace hkp
 
-// 16-B chunk swizzle of halo line L: physical chunk = logical ^ (L & 6).  A
-// fragment read covers 16 consecutive lines from ANY start (the tap offsets and
-// the 34-line patch rows put it anywhere), so the ring bodies' (row >> 1) & 7 —
-// conflict-free only from a 4-aligned start — cost ~3 extra LDS cycles per
-// ds_read_b128 here (0.30 of the halo kernels' LDS cycles, PMC r04); keyed on
-// bits 1-2 of L alone, every ds_read_b128 lane group of a read from any start
-// line hits 16 distinct 16-B bank slots (bit 0 of L picks the 128-B half, and the
-// group's two q values differ in bit 0 of the chunk).
-__device__ __forceinline__ int halo_swz(int L) { return L & 6; }
+// the halo, stem patch and DUO bodies: this translation unit's, in the order
+// they have always stood here (x3_start launches all of them from one switch)
+#include "x3_halo.h"
+#include "x3_stem.h"
+#include "x3_duo.h"
 
-// BNIN: the input is the producer's raw output and its BN + ReLU (+ the f16x3
-// split, P 3) is applied to each channel group's halo image in LDS after it
-// lands (X3Args::in_ss) — the bn_apply pass between the two convs disappears.
-// Each lane transforms whole 8-channel pieces: P 3 reads the piece's two fp32
-// chunks and writes its hi and lo chunks in place (the four pieces of a line are
-// four adjacent lanes of one wave instruction, so every read of the line precedes
-// its writes); P 1 rewrites one fp16 chunk.  Out-of-image lines are NaN lines
-// (relu(NaN*s + t) = 0).
-template <int P, bool BNIN>
-__device__ __forceinline__ void x3_halo_bnin(const X3Args& a, char* smem, int g, int tid) {
-    constexpr int ROW = 128;
-    constexpr int PIECES = P == 1 ? 8 : 4;                       // 8-channel pieces per line
-    constexpr int LPI = 512 / PIECES;                            // lines per block-wide pass
-    constexpr int NL = 8 * HALO_GA * 8;                          // halo lines incl. the dummies (384)
-    const int j = tid % PIECES;
-    const int c0 = g * (P == 1 ? 64 : 32) + 8 * j;
-    float sa[8], sb[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        sa[e] = a.in_ss[c0 + e];
-        sb[e] = a.in_ss[a.C + c0 + e];
-    }
-#pragma unroll
-    for (int L0 = 0; L0 < NL; L0 += LPI) {
-        const int L = L0 + tid / PIECES;
-        const int sw = halo_swz(L);
-        char* line = smem + L * ROW;
-        if constexpr (P == 1) {
-            f16x8* ch = (f16x8*)(line + ((j ^ sw) << 4));
-            const f16x8 v = *ch;
-            f16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float x = __fadd_rn(__fmul_rn((float)v[e], sa[e]), sb[e]);
-                o[e] = (_Float16)(x > 0.f ? x : 0.f);
-            }
-            *ch = o;
-        } else {
-            const f32x4 v0 = *(const f32x4*)(line + (((2 * j) ^ sw) << 4));
-            const f32x4 v1 = *(const f32x4*)(line + (((2 * j + 1) ^ sw) << 4));
-            f16x8 h, l;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float y = e < 4 ? v0[e] : v1[e - 4];
-                float x = __fadd_rn(__fmul_rn(y, sa[e]), sb[e]);
-                x = x > 0.f ? x : 0.f;
-                const _Float16 hv = (_Float16)x;
-                h[e] = hv;
-                l[e] = (_Float16)(x - (float)hv);
-            }
-            *(f16x8*)(line + ((j ^ sw) << 4)) = h;
-            *(f16x8*)(line + (((4 + j) ^ sw) << 4)) = l;
-        }
-    }
-}
-
-template <int P, bool BNIN>
-__device__ __forceinline__ void conv_x3_halo_body(const X3Args& a, char* smem) {
-    constexpr int BM = 256, BN = 64, WM = 4, WN = 2, ROW = 128;
-    constexpr int UM = BM / (WM * 16), UN = BN / (WN * 16);     // 4 x 2 16x16 sub-tiles per wave
-    static_assert(256 * (BN + 4) * 4 <= HALO_LDS && 8 * BN * 4 <= HALO_LDS, "epilogue staging");
-    static_assert(!BNIN || P == 3 || P == 1, "fused input BN: f16x3 or plain fp16");
-
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int mt = tile / a.n_tiles, nt = tile - mt * a.n_tiles;
-    const int pwn = a.Wo / HALO_PW, tpi = (a.Ho / HALO_PH) * pwn;
-    const int img = mt / tpi, rem = mt - img * tpi;
-    const int h0 = (rem / pwn) * HALO_PH, w0 = (rem - (rem / pwn) * pwn) * HALO_PW;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w / WN, wn = w % WN;
-    const int cstride = a.cch * 64;                             // halves per pixel
-    const int nks = a.nks;                                      // 9 taps x channel groups
-    const _Float16* zero = (const _Float16*)(BNIN ? g_x3_nan_line : g_x3_zero_line);
-
-    // ---- halo DMA: instruction i of wave w fills lines 8 (w*GA + i) .. +7 ----
-    unsigned h_off[HALO_GA];                                    // element offsets from a.xs (or ~0u: zero line)
-#pragma unroll
-    for (int i = 0; i < HALO_GA; ++i) {
-        const int L = 8 * (w * HALO_GA + i) + lane / 8;
-        const int Lc = (lane % 8) ^ halo_swz(L);
-        const int hl = L / HALO_LW, wl = L - hl * HALO_LW;
-        const int hi = h0 - 1 + hl, wi = w0 - 1 + wl;
-        const bool in = L < HALO_NL && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-        h_off[i] = in ? (unsigned)((((long)img * a.H + hi) * a.W + wi) * cstride + Lc * 8) : ~0u;
-    }
-    auto issue_halo = [&](int g) {
-#pragma unroll
-        for (int i = 0; i < HALO_GA; ++i)
-            glds16(h_off[i] != ~0u ? a.xs + ((unsigned long)h_off[i] + g * 64) : zero,
-                   smem + 8 * (w * HALO_GA + i) * ROW);
-    };
-    // ---- weight stage DMA: one instruction per wave, rows 8w .. 8w+7 ----
-    const int brow = 8 * w + lane / 8;
-    const int bline = a.RS * a.cch * 64;
-    const unsigned b_off = (unsigned)((n0 + brow) * bline + (((lane % 8) ^ ((brow >> 1) & 7)) * 8));
-    auto issue_b = [&](int t) {
-        const int g = t / 9, u = t - g * 9;
-        glds16(a.ws + (b_off + (unsigned)((u * a.cch + g) * 64)),
-               smem + HALO_ABYTES + (t % HALO_NSTB) * HALO_BSTAGE + 8 * w * ROW);
-    };
-
-    // ---- fragment addressing ----
-    const int r16 = lane & 15, q = lane >> 4;
-    int lb[UM];                                                 // halo line of tap (0, 0) for sub-tile i
-#pragma unroll
-    for (int i = 0; i < UM; ++i) {
-        const int m = wm * 64 + 16 * i + r16;
-        lb[i] = (m >> 5) * HALO_LW + (m & 31);
-    }
-    const int sw = (r16 >> 1) & 7;                              // B rows: 16-row tiles, as the ring's
-    const int fb_h = (wn * 32 + r16) * ROW + ((q ^ sw) << 4), fb_l = (wn * 32 + r16) * ROW + (((4 + q) ^ sw) << 4);
-
-    f32x4 acc[UM][UN];
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int j = 0; j < UN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto mfma = [](const f16x8& x, const f16x8& y, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0);
-    };
-
-    // column scale (weight scale x gradient scale), issued before the pipeline
-    const float ginv = a.amax ? 1.f / pow2_scale_for(a.amax) : 1.f;
-    float scv[UN];
-#pragma unroll
-    for (int j = 0; j < UN; ++j) scv[j] = (a.wscale ? a.wscale[n0 + wn * 32 + 16 * j + r16] : 1.f) * ginv;
-
-    // prologue: halo of group 0, weight stages 0 and 1
-    issue_halo(0);
-    issue_b(0);
-    if (nks > 1) issue_b(1);
-    if (nks > 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    if constexpr (BNIN) {
-        x3_halo_bnin<P, BNIN>(a, smem, 0, tid);
-        lds_sync();
-    }
-    for (int t = 0; t < nks; ++t) {
-        const int g = t / 9, u = t - g * 9;
-        const int toff = (u / 3) * HALO_LW + (u - (u / 3) * 3);
-        // fragments of step t
-        f16x8 ah[UM], al[UM], bh[UN], bl[UN];
-#pragma unroll
-        for (int i = 0; i < UM; ++i) {
-            const int L = lb[i] + toff;
-            const int ls = halo_swz(L);
-            ah[i] = *(const f16x8*)(smem + L * ROW + ((q ^ ls) << 4));
-            al[i] = *(const f16x8*)(smem + L * ROW + (((4 + q) ^ ls) << 4));
-        }
-        const char* bst = smem + HALO_ABYTES + (t % HALO_NSTB) * HALO_BSTAGE;
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            bh[j] = *(const f16x8*)(bst + j * 16 * ROW + fb_h);
-            bl[j] = *(const f16x8*)(bst + j * 16 * ROW + fb_l);
-        }
-        // weight stage t+2 goes into the slot step t-1 read (every wave is past
-        // this step's barrier, so done reading it)
-        if (t + 2 < nks) issue_b(t + 2);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int j = 0; j < UN; ++j) x3_products<P>(acc[i][j], ah[i], al[i], bh[j], bl[j], mfma);
-        if (t + 1 >= nks) break;
-        if (u == 8) {
-            // the group's last tap: every wave done with the halo, then the next
-            // group's halo (the youngest DMA: wait for everything)
-            lds_barrier();
-            issue_halo(g + 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (BNIN) {
-                lds_barrier();                                   // the whole halo landed
-                x3_halo_bnin<P, BNIN>(a, smem, g + 1, tid);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-        } else if (t + 2 < nks) {
-            asm volatile("s_waitcnt vmcnt(1)" ::: "memory");     // stage t+1 landed, t+2 in flight
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        lds_barrier();
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-    // ---- epilogue: BN tile partials (rows all valid: exact patch tiling), then
-    // the scaled tile staged through the drained LDS and written as 16-B row
-    // chunks; tile row m -> pixel (img, h0 + m/32, w0 + m%32) ----
-    const int rbase = m0 + wm * UM * 16 + 4 * q;
-    lds_sync();                                                  // every wave done with the halo / ring
-    if (a.part) {
-        x3_bn_partials_w<BN, UM, UN, 16, 16>(
-            a, (float*)smem, m0, n0, wm, wn, lane, [&](int i, int j) { return acc[i][j]; },
-            [&](int i, int r) { return rbase + i * 16 + r; }, [&](int j) { return scv[j]; }, (float*)smem);
-        lds_sync();
-    }
-    auto out_pix = [&](int row) { return ((long)img * a.Ho + h0 + (row >> 5)) * a.Wo + w0 + (row & 31); };
-    if constexpr (P == 1) {
-        constexpr int PITCH = BN + 8, CH = BN / 8;
-        _Float16* st = (_Float16*)smem;
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int j = 0; j < UN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    st[(wm * UM * 16 + i * 16 + 4 * q + r) * PITCH + wn * 32 + j * 16 + r16] =
-                        (_Float16)(acc[i][j][r] * scv[j]);
-        lds_sync();
-#pragma unroll 4
-        for (int e = tid; e < BM * CH; e += 512) {
-            const int row = e / CH, cc = e - row * CH;
-            x3_st16((uint4*)(a.y16 + out_pix(row) * a.K + n0 + cc * 8), *(const uint4*)(smem + (row * PITCH + cc * 8) * 2), a.st_kind, 1);
-        }
-    } else {
-        constexpr int PITCH = BN + 4, C4 = BN / 4;
-        float* st = (float*)smem;
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int j = 0; j < UN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    st[(wm * UM * 16 + i * 16 + 4 * q + r) * PITCH + wn * 32 + j * 16 + r16] = acc[i][j][r] * scv[j];
-        lds_sync();
-#pragma unroll 4
-        for (int e = tid; e < BM * C4; e += 512) {
-            const int row = e / C4, c4 = e - row * C4;
-            const long off = out_pix(row) * a.K + n0 + c4 * 4;
-            f32x4 v = *(const f32x4*)(st + row * PITCH + c4 * 4);
-            if (a.add) {
-                const f32x4 ad = *(const f32x4*)(a.add + off);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = v[k] + ad[k];
-            }
-            *(f32x4*)(a.y + off) = v;
-        }
-    }
-}
-
-template <int P>
-__global__ __launch_bounds__(512, 2) void conv_x3_halo_kernel(X3Args a) {
-    __shared__ __attribute__((aligned(1024))) char smem[HALO_LDS];
-    conv_x3_halo_body<P, false>(a, smem);
-}
-
-// the same with the input's BN + ReLU applied to each halo image (X3Args::in_ss)
-template <int P>
-__global__ __launch_bounds__(512, 2) void conv_x3_halo_bnin_kernel(X3Args a) {
-    __shared__ __attribute__((aligned(1024))) char smem[HALO_LDS];
-    conv_x3_halo_body<P, true>(a, smem);
-}
-
-// ---------------------------------------------------------------------------
-// Stem patch body (conv_x3_stem_patch_kernel): the 7x7/s2 stem on the padded
-// NHWC4 hi | lo image planes of hkp_stem_pack_x3, a tile = an 8 x 32 patch of
-// output pixels.  The one-tile stem (conv_x3_kernel<64, STEM, PAIR>) stages per
-// filter row a 256-line im2col window — pixels 2wo .. 2wo+7 of one padded row for
-// every output pixel, each input pixel fetched ~4x per row and 7 rows deep: 224 KB
-// of L2 -> LDS traffic per tile, the stem's bound (C2 288 us for 629 MB of output).
-// Here the patch's (2*8+5) x (2*32+6) = 21 x 70 padded pixels of both planes
-// (23 KB) and all 7 filter rows of the 64 weight rows (56 KB) are staged ONCE by
-// LDS-DMA and the 7 K-steps read their fragments from them with no barrier between:
-// output pixel (i, j), filter row r, chunk q (taps 2q, 2q+1 x 4 channels) is the
-// 16 B at patch row 2i + r, pixel 2j + 2q — 16 consecutive pixels of a fragment
-// read 256 contiguous bytes (every bank once).  B lines keep the ring bodies'
-// (row >> 1) & 7 chunk swizzle.  256 x 64 tile, 8 waves 4 x 2 (wave tile 64 x 32),
-// 16x16x32 MFMAs, 80 KiB: two blocks per CU, one's epilogue beside the other's
-// MFMAs; epilogue = the halo body's (BN tile partials, LDS-staged fp32 row chunks).
-constexpr int STEM_PR = 2 * STEM_PH + 5, STEM_PC = 2 * STEM_PW + 6;   // 21 x 70 pixels (STEM_PH x STEM_PW patches: x3_plan.h)
-constexpr int STEM_PLANE = STEM_PR * STEM_PC * 8;                // bytes per plane (4 ch fp16 per pixel)
-constexpr int STEM_BBYTES = 7 * 64 * 128;                        // 7 filter rows x 64 weight lines
-constexpr int STEM_PCH = 2 * STEM_PLANE / 16;                    // patch 16-B chunks (1470)
-constexpr int STEM_PGA = (STEM_PCH + 511) / 512;                 // patch DMA instructions per wave (3)
-constexpr int STEM_LDS = STEM_BBYTES + 8 * STEM_PGA * 1024;      // B, then the patch (+ dummy chunks): 80 KiB
-
-HKP_AB_KNOB(int, g_stem_pair, 0);                               // hkp_debug_stem_pair
-
-// SRC: 0 the padded hi | lo planes of hkp_stem_pack_x3 (DMA), 1 the fp32 NCHW image,
-// 2 the uint8 NHWC (BGR) batch — for 1 / 2 the patch is built in LDS from the image
-// itself (hkp_stem_pack_x3's arithmetic: x = u8 / 255 for uint8, hi = f16(x),
-// lo = f16(x - hi), zeros outside the image and in channels C..3), so the planes
-// are never written (a.H / a.W / a.C: the image's height, width, channels)
-template <int SRC>
-__global__ __launch_bounds__(512, 2) void conv_x3_stem_patch_kernel(X3Args a) {
-    __shared__ __attribute__((aligned(1024))) char smem[STEM_LDS];
-    constexpr int BM = 256, BN = 64, WM = 4, WN = 2, ROW = 128;
-    constexpr int UM = BM / (WM * 16), UN = BN / (WN * 16);     // 4 x 2 16x16 sub-tiles per wave
-    static_assert(256 * (BN + 4) * 4 <= STEM_LDS && STEM_PGA * 512 >= STEM_PCH, "stem patch LDS");
-    x3_stamp(a, 0);
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int mt = tile / a.n_tiles, nt = tile - mt * a.n_tiles;
-    const int pwn = a.Wo / STEM_PW, tpi = (a.Ho / STEM_PH) * pwn;
-    const int img = mt / tpi, rem = mt - img * tpi;
-    const int h0 = (rem / pwn) * STEM_PH, w0 = (rem - (rem / pwn) * pwn) * STEM_PW;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w / WN, wn = w % WN;
-
-    // ---- staging: the weight lines (7 instructions per wave: LDS row R = r*64 + n
-    // holds logical chunk p ^ ((n >> 1) & 7) at physical chunk p), then the patch
-    // (chunk c: plane c / (PLANE/16), patch row, 16-B column — 35 per row, the 70
-    // padded pixels of a patch row are contiguous in the plane) ----
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        const int R = 8 * (w * 7 + i) + lane / 8;
-        const int r = R >> 6, n = R & 63;
-        const int Lc = (lane % 8) ^ ((n >> 1) & 7);
-        glds16(a.ws + ((long)(n0 + n) * 7 + r) * 64 + Lc * 8, smem + 8 * (w * 7 + i) * ROW);
-    }
-    if constexpr (SRC == 0) {
-        const _Float16* zero = (const _Float16*)g_x3_zero_line;
-        const long prow0 = ((long)img * a.H + 2 * h0) * a.W + 2 * w0;   // padded pixel of patch (0, 0)
-#pragma unroll
-        for (int i = 0; i < STEM_PGA; ++i) {
-            const int c = 512 * i + 64 * w + lane;               // instruction i of wave w: chunks 512 i + 64 w + lane
-            const int pl = c >= STEM_PLANE / 16 ? 1 : 0, cc = c - pl * (STEM_PLANE / 16);
-            const int pr = cc / (STEM_PC / 2), pc = cc - pr * (STEM_PC / 2);
-            const _Float16* src = c < STEM_PCH ? a.xs + pl * a.plane + (prow0 + (long)pr * a.W) * 4 + pc * 8 : zero;
-            glds16(src, smem + STEM_BBYTES + (512 * i + 64 * w) * 16);
-        }
-    } else {
-        // padded pixel (pr, pc) of the patch = image pixel (2 h0 + pr - 3, 2 w0 + pc - 3);
-        // every load of the thread's pixels issued before the first conversion
-        constexpr int NPX = STEM_PR * STEM_PC, IT = (NPX + 511) / 512;
-        f32x4 v[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int px = tid + 512 * it;
-            const int pr = px / STEM_PC, pc = px - pr * STEM_PC;
-            const int h = 2 * h0 + pr - 3, wi = 2 * w0 + pc - 3;
-            const bool in = px < NPX && (unsigned)h < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-            v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (in && c < a.C) {
-                    if constexpr (SRC == 2)
-                        v[it][c] = __fdiv_rn((float)((const uint8_t*)a.xs)[(((long)img * a.H + h) * a.W + wi) * a.C + c], 255.f);
-                    else
-                        v[it][c] = ((const float*)a.xs)[(((long)img * a.C + c) * a.H + h) * a.W + wi];
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int px = tid + 512 * it;
-            if (px >= NPX) break;
-            h16x4 hv, lv;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const _Float16 hh = (_Float16)v[it][c];
-                hv[c] = hh;
-                lv[c] = (_Float16)(v[it][c] - (float)hh);
-            }
-            *(h16x4*)(smem + STEM_BBYTES + px * 8) = hv;
-            *(h16x4*)(smem + STEM_BBYTES + STEM_PLANE + px * 8) = lv;
-        }
-    }
-
-    // ---- fragment addressing ----
-    const int r16 = lane & 15, q = lane >> 4;
-    int aoff[UM];                                               // patch byte offset of sub-tile i's pixel, filter row 0, chunk q
-#pragma unroll
-    for (int i = 0; i < UM; ++i) {
-        const int m = wm * 64 + 16 * i + r16;
-        aoff[i] = STEM_BBYTES + ((2 * (m >> 5)) * STEM_PC + 2 * (m & 31) + 2 * q) * 8;
-    }
-    const int sw = (r16 >> 1) & 7;
-    const int fb_h = (wn * 32 + r16) * ROW + ((q ^ sw) << 4), fb_l = (wn * 32 + r16) * ROW + (((4 + q) ^ sw) << 4);
-
-    f32x4 acc[UM][UN];
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int j = 0; j < UN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto mfma = [](const f16x8& x, const f16x8& y, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0);
-    };
-    float scv[UN];
-#pragma unroll
-    for (int j = 0; j < UN; ++j) scv[j] = a.wscale ? a.wscale[n0 + wn * 32 + 16 * j + r16] : 1.f;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    x3_stamp(a, 1);
-    // 7 K-steps (filter rows) from the resident patch and weights: no barriers
-    f16x8 ah[UM], al[UM], bh[UN], bl[UN];
-    auto read_frags = [&](int r) {
-#pragma unroll
-        for (int i = 0; i < UM; ++i) {
-            ah[i] = *(const f16x8*)(smem + aoff[i] + r * STEM_PC * 8);
-            al[i] = *(const f16x8*)(smem + aoff[i] + r * STEM_PC * 8 + STEM_PLANE);
-        }
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            bh[j] = *(const f16x8*)(smem + r * 64 * ROW + j * 16 * ROW + fb_h);
-            bl[j] = *(const f16x8*)(smem + r * 64 * ROW + j * 16 * ROW + fb_l);
-        }
-    };
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-        read_frags(r);
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int j = 0; j < UN; ++j) x3_products<3>(acc[i][j], ah[i], al[i], bh[j], bl[j], mfma);
-    }
-    x3_stamp(a, 2);
-
-    // ---- epilogue: BN tile partials (rows all valid: exact patch tiling), the
-    // scaled tile staged through the LDS and written as 16-B row chunks; tile row
-    // m -> output pixel (img, h0 + m/32, w0 + m%32) ----
-    const int rbase = m0 + wm * UM * 16 + 4 * q;
-    lds_sync();                                                  // every wave done with the patch and weights
-    if (a.part) {
-        x3_bn_partials_w<BN, UM, UN, 16, 16>(
-            a, (float*)smem, m0, n0, wm, wn, lane, [&](int i, int j) { return acc[i][j]; },
-            [&](int i, int r) { return rbase + i * 16 + r; }, [&](int j) { return scv[j]; }, (float*)smem);
-        lds_sync();
-    }
-    x3_stamp(a, 3);
-    constexpr int PITCH = BN + 4, C4 = BN / 4;
-    float* st = (float*)smem;
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int j = 0; j < UN; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                st[(wm * UM * 16 + i * 16 + 4 * q + r) * PITCH + wn * 32 + j * 16 + r16] = acc[i][j][r] * scv[j];
-    lds_sync();
-    x3_stamp(a, 4);
-#pragma unroll 4
-    for (int e = tid; e < BM * C4; e += 512) {
-        const int row = e / C4, c4 = e - row * C4;
-        const long off = (((long)img * a.Ho + h0 + (row >> 5)) * a.Wo + w0 + (row & 31)) * a.K + n0 + c4 * 4;
-        x3_st16((f32x4*)(a.y + off), *(const f32x4*)(st + row * PITCH + c4 * 4), a.st_kind, 2);
-    }
-    x3_stamp(a, 5);
-}
-
-
-// ---------------------------------------------------------------------------
-// DUO body (conv_x3_duo_kernel<1>): plain-fp16 (P 1, config C4) convs on 256 x 128
-// tiles run by TWO 4-wave blocks per CU.  The one-tile 256x256 bodies hold a
-// whole CU, so each tile's pipeline fill, BN partials, fp16 staging and stores
-// run with the CU's matrix pipes idle — on C4's short-K 1x1 GEMMs (8-16 K-steps
-// per tile) about half of a tile's time (DESIGN "C4's 1x1 GEMMs").  Here two
-// independent blocks share the CU: one block's fill and epilogue run beside the
-// other's K loop, and their vmcnt / barriers are separate (a persistent body's
-// epilogue stores, by contrast, shared vmcnt with its next tile's DMA).
-// Per block: 4 waves as 2 x 2, wave tile 128 x 64 (8 x 4 16x16x32 MFMA tiles,
-// 128 accumulator registers); a 3-stage LDS ring of HALF lines — a stage holds
-// 32 channels (64 B) of every A row (256) and B row (128): 24 KiB — so three
-// stages (72 KiB, which also holds the fp16 epilogue tile) fit twice per CU.
-// K order: channel group (64 channels), tap, half; a half-line is one k32 step,
-// one MFMA per (16-row, 16-column) pair.  64-B rows: lane l of a DMA piece writes
-// row l/4, 16-B chunk l%4; the chunk swizzle (4 - (row >> 2)) & 3 makes every
-// ds_read_b128 lane group of the fragment reads (rows r16 = lane & 15, chunk
-// lane >> 4) hit 16 distinct 16-B bank groups.  Epilogue: BN partials per
-// 128-row half straight from one wave's accumulators (a wave holds a whole
-// half: no LDS merge), then the fp16 tile staged in the drained ring and written
-// as 16-B row chunks, optionally through the fused BN + residual + ReLU
-// (hkp_conv2d_fwd_f16_bn) — the 256x256 body's arithmetic, element for element.
-constexpr int DUO_BM = 256, DUO_ROW = 64, DUO_NST = 3;              // (DUO_BN = 128: x3_plan.h)
-// first-round arrivals per CU (key: XCC id x the HW_ID's SE / SH / CU bits): the
-// second block to arrive on a CU starts late, so the two blocks sharing it run
-// half a block apart (see conv_x3_duo_kernel); parity of a running count, never reset
-__device__ unsigned g_duo_cu_cnt[8 * 128];
-constexpr int DUO_STAGE = (DUO_BM + DUO_BN) * DUO_ROW;                 // 24 KiB
-constexpr int DUO_LDS = DUO_NST * DUO_STAGE;                           // 72 KiB: two blocks per CU
-static_assert(DUO_BM * (DUO_BN + 8) * 2 + 4 * DUO_BN * 4 <= DUO_LDS, "DUO epilogue staging");
-
-__device__ __forceinline__ int duo_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
-
-// BN partials (sum, M2 about the half's mean) of one wave's 128-row half of the
-// tile: each lane reduces its 32 rows of a column, then lanes l, l^16, l^32, l^48
-// (the column's four row groups) merge by Chan's formula — equal counts, so the
-// factors are constants and the result is symmetric in each pair (all four lanes
-// hold the same bits).  Rows past M (the last tile) take the counted form.
-template <int UM, int UN>
-__device__ __forceinline__ void duo_bn_partials(const X3Args& a, const f32x4 (&acc)[UM][UN], const float (&sc)[UN],
-                                                int m0h, int ncol0, int lane) {
-    const int q = lane >> 4, r16 = lane & 15;
-    const long tile128 = (long)(m0h >> 7);
-    if (m0h + 128 <= a.M) {                                  // block-uniform
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            f32x4 s4 = acc[0][j];
-#pragma unroll
-            for (int i = 1; i < UM; ++i) s4 += acc[i][j];
-            float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-            constexpr float inv = 1.f / (UM * 4);
-            const f32x4 mu = {s * inv, s * inv, s * inv, s * inv};
-            f32x4 q4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < UM; ++i) {
-                const f32x4 d = acc[i][j] - mu;
-                q4 += d * d;
-            }
-            float m2 = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-            x3_chan_merge(s, m2, __shfl_xor(s, 16), __shfl_xor(m2, 16), 1.f / (UM * 4), UM * 2.f);
-            x3_chan_merge(s, m2, __shfl_xor(s, 32), __shfl_xor(m2, 32), 1.f / (UM * 8), UM * 4.f);
-            if (q == 0) {
-                const int c = ncol0 + 16 * j + r16;
-                a.part[(tile128 * a.K + c) * 2 + 0] = s * sc[j];
-                a.part[(tile128 * a.K + c) * 2 + 1] = m2 * (sc[j] * sc[j]);
-            }
-        }
-        return;
-    }
-    if (m0h >= a.M) return;
-    float ln = 0.f;
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ln += (m0h + 16 * i + 4 * q + r < a.M) ? 1.f : 0.f;
-    const float linv = ln > 0.f ? 1.f / ln : 0.f;
-#pragma unroll
-    for (int j = 0; j < UN; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s += (m0h + 16 * i + 4 * q + r < a.M) ? acc[i][j][r] : 0.f;
-        const float mu = s * linv;
-        float m2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < UM; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float d = acc[i][j][r] - mu;
-                m2 += (m0h + 16 * i + 4 * q + r < a.M) ? d * d : 0.f;
-            }
-        float n = ln;
-        for (int o = 16; o < 64; o <<= 1) {
-            const float nb = __shfl_xor(n, o), sb = __shfl_xor(s, o), qb = __shfl_xor(m2, o);
-            const float nt = n + nb;
-            const float f = nt > 0.f ? n * nb / nt : 0.f;
-            const float ia = n > 0.f ? 1.f / n : 0.f, ib = nb > 0.f ? 1.f / nb : 0.f;
-            const float d = sb * ib - s * ia;
-            s = s + sb;
-            m2 = (m2 + qb) + d * d * f;
-            n = nt;
-        }
-        if (q == 0) {
-            const int c = ncol0 + 16 * j + r16;
-            a.part[(tile128 * a.K + c) * 2 + 0] = s * sc[j];
-            a.part[(tile128 * a.K + c) * 2 + 1] = m2 * (sc[j] * sc[j]);
-        }
-    }
-}
-
-template <int P>
-__global__ __launch_bounds__(256, 2) void conv_x3_duo_kernel(X3Args a) {
-    static_assert(P == 1, "DUO: the plain-fp16 operand layout");
-    __shared__ __attribute__((aligned(1024))) char smem[DUO_LDS];
-    constexpr int BM = DUO_BM, BN = DUO_BN, ROW = DUO_ROW, NST = DUO_NST, STAGE = DUO_STAGE;
-    constexpr int UM = 8, UN = 4;                    // 16x16 tiles per wave (wave tile 128 x 64)
-    constexpr int GA = 4, GB = 2, GL = GA + GB;      // DMA pieces (16 rows each) per wave per stage
-
-    x3_stamp(a, 0);
-    x3_stamp_where(a);
-    // Co-resident blocks of a one-round-per-tile grid start together and, doing the
-    // same work, stay in phase: both fill, both run the K loop, both run the
-    // epilogue — nothing overlaps.  In the first round the second block to arrive
-    // on each CU waits about half a block's lifetime (X3Args::stagger_ticks), so
-    // from then on one block's fill and epilogue run beside the other's K loop.
-    if (a.stagger_ticks > 0 && blockIdx.x < (unsigned)a.stagger_blocks) {
-        __shared__ int late;
-        if (threadIdx.x == 0) {
-            const unsigned hw = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID
-            const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
-            const unsigned key = (xcc & 7) * 128 + ((hw >> 8) & 127);
-            late = (int)(atomicAdd(&g_duo_cu_cnt[key], 1u) & 1u);
-        }
-        __syncthreads();
-        if (late) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)a.stagger_ticks) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int mt = tile / a.n_tiles, nt = tile - mt * a.n_tiles;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w >> 1, wn = w & 1;
-    const int nst = 2 * a.nks;                       // half-line stages
-
-    // ---- DMA sources (the one-tile bodies' bookkeeping, 64-B rows) ----
-    const int cstride = a.cch * 64;                  // halves per pixel
-    const long xbias = (long)a.pad * (a.W + 1) * cstride;
-    const _Float16* xbase = a.xs - xbias;
-    const _Float16* zero = (const _Float16*)g_x3_zero_line;
-    int a_org[GA];
-    unsigned a_off[GA];
-#pragma unroll
-    for (int i = 0; i < GA; ++i) {
-        const int row = 64 * w + 16 * i + (lane >> 2);
-        const int Lc = (lane & 3) ^ duo_swz(row);
-#ifdef HKP_AB_KNOBS
-        const int m = a.a_wrap ? (m0 + row) % a.a_wrap : m0 + row;
-#else
-        const int m = m0 + row;
-#endif
-        int hb = -16384, wb = -16384;
-        long off = 0;
-        if (m < a.M) {
-            const int hw = a.Ho * a.Wo;
-            const int n = m / hw, rem = m - n * hw;
-            const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-            hb = ho * a.stride - a.pad;
-            wb = wo * a.stride - a.pad;
-            off = (((long)n * a.H + hb) * a.W + wb) * cstride + Lc * 8;
-        }
-        a_org[i] = (int)(((unsigned)hb << 16) | ((unsigned)wb & 0xFFFFu));
-        a_off[i] = (unsigned)(off + xbias);
-    }
-    const int bline = a.RS * a.cch * 64;             // halves per weight row
-    int b_off[GB];
-#pragma unroll
-    for (int j = 0; j < GB; ++j) {
-        const int row = 32 * w + 16 * j + (lane >> 2);
-        b_off[j] = (n0 + row) * bline + ((lane & 3) ^ duo_swz(row)) * 8;
-    }
-    // staging position of the next stage to issue: (channel group, tap, half)
-    int q_buf = 0, q_cc = 0, q_tap = 0, q_rr = 0, q_ss = 0, q_half = 0;
-    auto issue = [&]() {
-        char* st = smem + q_buf * STAGE;
-        const int dh = q_rr * a.dil, dw = q_ss * a.dil;
-        const long toff = ((long)dh * a.W + dw) * cstride + q_cc * 64 + q_half * 32;
-#pragma unroll
-        for (int i = 0; i < GA; ++i) {
-            const int hb = a_org[i] >> 16, wb = (int)(short)(a_org[i] & 0xFFFF);
-            const bool in = (unsigned)(hb + dh) < (unsigned)a.H && (unsigned)(wb + dw) < (unsigned)a.W;
-            glds16(in ? xbase + ((unsigned long)a_off[i] + toff) : zero, st + (64 * w + 16 * i) * ROW);
-        }
-        const int boff = (q_tap * a.cch + q_cc) * 64 + q_half * 32;
-#pragma unroll
-        for (int j = 0; j < GB; ++j) glds16(a.ws + (unsigned)(b_off[j] + boff), st + (BM + 32 * w + 16 * j) * ROW);
-        q_buf = q_buf == NST - 1 ? 0 : q_buf + 1;
-        if (++q_half == 2) {
-            q_half = 0;
-            if (++q_ss == a.S) {
-                q_ss = 0;
-                ++q_rr;
-            }
-            if (++q_tap == a.RS) {
-                q_tap = 0;
-                q_rr = 0;
-                ++q_cc;
-            }
-        }
-    };
-
-    // ---- fragments: lane reads row r16 of a 16-row tile, logical chunk q ----
-    const int r16 = lane & 15, q = lane >> 4;
-    const int fo = r16 * ROW + ((q ^ duo_swz(r16)) << 4);
-    const int a_base = (wm * 128) * ROW + fo, b_base = (BM + wn * 64) * ROW + fo;
-    f32x4 acc[UM][UN];
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int j = 0; j < UN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f16x8 fa[UM], fb[UN];
-    auto read_a = [&](const char* st) {
-#pragma unroll
-        for (int i = 0; i < UM; ++i) fa[i] = *(const f16x8*)(st + a_base + i * 16 * ROW);
-    };
-    auto read_b = [&](int j, const char* st) { fb[j] = *(const f16x8*)(st + b_base + j * 16 * ROW); };
-    auto mma_col = [&](int j) {
-#pragma unroll
-        for (int i = 0; i < UM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    };
-
-    // column scales (weight scale), issued before the fill
-    float sc[UN];
-#pragma unroll
-    for (int j = 0; j < UN; ++j) sc[j] = a.wscale ? a.wscale[n0 + wn * 64 + 16 * j + r16] : 1.f;
-
-    // ---- pipeline (the 3-stage ring schedule of conv_x3_mf16_body): per stage t —
-    // wait own DMA of t+1 (t+2 stays in flight), barrier, DMA of t+3 into t's
-    // buffer (its fragments were read during step t-1) spread over the columns,
-    // per column j [MFMAs of t with B_j] [read B_j of t+1], then A of t+1 ----
-    for (int s = 0; s < NST; ++s)
-        if (s < nst) issue();
-    {
-        const int after = min(nst, NST) - 1;
-        if (after >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GL) : "memory");
-        else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    lds_barrier();
-    x3_stamp(a, 1);
-    read_a(smem);
-#pragma unroll
-    for (int j = 0; j < UN; ++j) read_b(j, smem);
-    int cur = 0;
-    auto kstep = [&](const int t, const bool dma) {
-        if (t + 2 < nst) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GL) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        lds_barrier();
-        cur = cur == NST - 1 ? 0 : cur + 1;
-        const char* st = smem + cur * STAGE;
-        if (dma) issue();
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            mma_col(j);
-            read_b(j, st);
-        }
-        read_a(st);
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            __builtin_amdgcn_sched_group_barrier(0x008, UM, 0);     // column j's MFMAs
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // refill B_j
-            if (dma && j * ((GL + UN - 1) / UN) < GL)
-                __builtin_amdgcn_sched_group_barrier(0x020, (GL + UN - 1) / UN, 0);   // DMA pieces
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, UM, 0);         // next A frags
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    int t = 0;
-    for (; t + 3 < nst; ++t) kstep(t, true);
-    for (; t + 1 < nst; ++t) kstep(t, false);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < UN; ++j) mma_col(j);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA in flight into the ring past here
-    x3_stamp(a, 2);
-
-    // ---- epilogue: BN partials of this wave's 128-row half, then the fp16 tile ----
-    if (a.part) duo_bn_partials<UM, UN>(a, acc, sc, m0 + 128 * wm, n0 + wn * 64, lane);
-    x3_stamp(a, 3);
-    constexpr int PITCH = BN + 8, CH = BN / 8, SS_OFF = BM * PITCH * 2;
-    constexpr int NT = 256, NPT = BM * CH / NT;              // 16-B chunks per thread
-    static_assert(NT % CH == 0, "a thread keeps its 8 channels");
-    const int cc = tid % CH;
-    // fused BN epilogue: per-column parameters and the residual chunks in flight
-    // before the tile is staged (their latency hides behind it)
-    float ep0 = 0.f, ep1 = 0.f;
-    f16x8 res[NPT];
-    if (a.ep_ss) {
-        const int h = tid / BN, c = tid - h * BN;                // tid < 2 * BN: all 256 threads
-        ep0 = a.ep_ss[h * a.K + n0 + c];
-        ep1 = a.ep_rss ? a.ep_rss[h * a.K + n0 + c] : 0.f;
-#pragma unroll
-        for (int u = 0; u < NPT; ++u) {
-            const int row = (tid + NT * u) / CH, m = m0 + row;
-            res[u] = f16x8{};
-            if (a.ep_res && m < a.M)
-                res[u] = __builtin_nontemporal_load((const f16x8*)(a.ep_res + (long)m * a.K + n0 + cc * 8));
-        }
-    }
-    lds_sync();                                              // every wave done reading the ring
-    _Float16* tl = (_Float16*)smem;
-#pragma unroll
-    for (int i = 0; i < UM; ++i)
-#pragma unroll
-        for (int j = 0; j < UN; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                tl[(wm * 128 + i * 16 + 4 * q + r) * PITCH + wn * 64 + j * 16 + r16] = (_Float16)(acc[i][j][r] * sc[j]);
-    float* ssl = (float*)(smem + SS_OFF);                    // [4][BN]: scale, shift, residual scale, shift
-    if (a.ep_ss) {
-        ssl[tid] = ep0;
-        ssl[2 * BN + tid] = ep1;
-    }
-    lds_sync();
-    x3_stamp(a, 4);
-    if (!a.ep_ss) {
-#pragma unroll 4
-        for (int u = 0; u < NPT; ++u) {
-            const int row = (tid + NT * u) / CH, m = m0 + row;
-            if (m < a.M)
-                x3_st16((uint4*)(a.y16 + (long)m * a.K + n0 + cc * 8), *(const uint4*)(smem + (row * PITCH + cc * 8) * 2), a.st_kind, 1);
-        }
-        x3_stamp(a, 5);
-        return;
-    }
-    float sa[8], sb[8], ra[8], rb[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        sa[e] = ssl[cc * 8 + e];
-        sb[e] = ssl[BN + cc * 8 + e];
-        ra[e] = ssl[2 * BN + cc * 8 + e];
-        rb[e] = ssl[3 * BN + cc * 8 + e];
-    }
-    const bool hres = a.ep_res != nullptr, rsc = a.ep_rss != nullptr, relu = a.ep_relu != 0;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-        const int row = (tid + NT * u) / CH, m = m0 + row;
-        if (m >= a.M) continue;
-        const f16x8 v = *(const f16x8*)(smem + (row * PITCH + cc * 8) * 2);
-        const f16x8 rv = res[u];
-        f16x8 h;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float o = __fadd_rn(__fmul_rn((float)v[k], sa[k]), sb[k]);
-            if (hres) o = rsc ? __fadd_rn(o, __fadd_rn(__fmul_rn((float)rv[k], ra[k]), rb[k])) : __fadd_rn(o, (float)rv[k]);
-            if (relu) o = o > 0.f ? o : 0.f;
-            h[k] = (_Float16)o;
-        }
-        x3_st16((f16x8*)(a.y16 + (long)m * a.K + n0 + cc * 8), h, a.st_kind, 2);
-    }
-    x3_stamp(a, 5);
-}
-
-// ---------------------------------------------------------------------------
-// operand packing
-
-__device__ __forceinline__ void split_store(float v, _Float16* hi_p) {   // hi at p, lo at p + 32
-    const _Float16 h = (_Float16)v;
-    hi_p[0] = h;
-    hi_p[32] = (_Float16)(v - (float)h);
-}
-
-// block max |x| over a row of n elements addressed by idx(i); result broadcast
-template <typename F>
-__device__ __forceinline__ float block_absmax(int n, F&& val) {
-    __shared__ float red[8];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, fabsf(val(i)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    float r = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r = fmaxf(r, red[i]);
-    __syncthreads();
-    return r;
-}
-
-// w[k][tap][c] fp32 (KRSC) * 2^e_k → ws[k][tap][c/32][hi32|lo32]; one block per k.
-// Element e → 2e - (c&31) (lo 32 halves later); wscale[k] = 2^-e_k.
-__global__ __launch_bounds__(256) void weight_pack_x3_kernel(int rsc, const float* __restrict__ w,
-                                                            _Float16* __restrict__ ws, float* __restrict__ wscale) {
-    const int k = blockIdx.x;
-    const float* row = w + (long)k * rsc;
-    const float sc = pow2_scale_of(block_absmax(rsc, [&](int i) { return row[i]; }));
-    for (int i = threadIdx.x; i < rsc; i += blockDim.x) {
-        const long e = (long)k * rsc + i;
-        split_store(row[i] * sc, ws + 2 * e - (e & 31));
-    }
-    if (threadIdx.x == 0) wscale[k] = 1.f / sc;
-}
-
-// w[k][tap][c] fp32 (KRSC) * 2^e_k → fp16 KRSC (the plain-fp16 conv's operand:
-// 64-channel 128-B lines); one block per k, wscale[k] = 2^-e_k
-__global__ __launch_bounds__(256) void weight_pack_f16_kernel(int rsc, const float* __restrict__ w,
-                                                             _Float16* __restrict__ out, float* __restrict__ wscale) {
-    const int k = blockIdx.x;
-    const float* row = w + (long)k * rsc;
-    const float sc = pow2_scale_of(block_absmax(rsc, [&](int i) { return row[i]; }));
-    for (int i = threadIdx.x; i < rsc; i += blockDim.x) out[(long)k * rsc + i] = (_Float16)(row[i] * sc);
-    if (threadIdx.x == 0) wscale[k] = 1.f / sc;
-}
-
-// flipped dgrad weight, packed: row c (forward input channel) holds element
-// (r', s', k) = w[k][R-1-r'][S-1-s'][c] * 2^e_c; one block per c
-__global__ __launch_bounds__(256) void weight_flip_pack_x3_kernel(int K, int R, int S, int C,
-                                                                 const float* __restrict__ w,
-                                                                 _Float16* __restrict__ out,
-                                                                 float* __restrict__ wscale) {
-    const int c = blockIdx.x;
-    const int n = R * S * K;
-    auto val = [&](int i) {
-        const int k = i % K, t = i / K, sp = t % S, rp = t / S;
-        return w[(((long)k * R + (R - 1 - rp)) * S + (S - 1 - sp)) * C + c];
-    };
-    const float sc = pow2_scale_of(block_absmax(n, val));
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const long e = (long)c * n + i;
-        split_store(val(i) * sc, out + 2 * e - (e & 31));
-    }
-    if (threadIdx.x == 0) wscale[c] = 1.f / sc;
-}
-
-// x * 2^e (e from amax; 1 without) → packed split [P][C/32][hi32|lo32]
-__global__ __launch_bounds__(256) void split_pack_x3_kernel(long n4, const f32x4* __restrict__ x,
-                                                           const unsigned* __restrict__ amax,
-                                                           _Float16* __restrict__ out) {
-    const float sc = pow2_scale_for(amax);
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        f32x4 v = x[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= sc;
-        store_split4(v, i, out, 3);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Weight gradient on packed split operands:
-//     dW[k][tap][c] = sum_p dy[p][k] * x[pixel(p, tap)][c]        (p: output pixels)
-// GEMM rows = Cout (dy side, KA per tile), columns = (tap, c) flattened (x side,
-// 256 per tile = 8 channel groups, one per wave for staging), reduction over
-// output pixels, split-K over pixel ranges into fixed-order fp32 slabs
-// [split][K][R*S*C] (summed by wg_x3_reduce_kernel — deterministic).
-// Both LDS images are pixel-major per channel group: line (group, pixel) =
-// 128 B [hi32|lo32], 32 pixels per K-step, written by LDS-DMA; the MFMA
-// fragments (8 consecutive pixels of one channel per lane) come from
-// ds_read_b64_tr_b16 transposed reads.  Swizzle: 16-B chunk ^= ((pixel>>1)&1)<<2
-// makes every 32-lane half of a transposed read cover all 64 banks once.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-struct WgX3Args {
-    const _Float16* xs;     // packed x  [N*H*W][C/32][64]
-    const _Float16* dys;    // packed, scaled dy [M][K/32][64]
-    const unsigned* amax;   // the scale dy was split with (pow2_scale_for), nullable
-    float* ws;              // slabs [splits][K][RSC]
-    int N, H, W, C, K, R, S, stride, pad, dil, Ho, Wo;
-    int M, RSC, r_tiles, mps, tiles;
-};
-
-// ds_read_b64_tr_b16 as inline asm: the builtin makes hipcc drain the whole
-// LDS-DMA queue (vmcnt(0)) before every transposed read, since it cannot tell
-// the read from the in-flight DMA's destination.  The caller waits lgkmcnt
-// itself before the MFMAs that consume the result (explicit waits below, each
-// followed by sched_barrier(0) so no MFMA is scheduled ahead of it).
-template <int OFF>
-__device__ __forceinline__ s16x4 ds_tr16(unsigned lds_addr) {
-    s16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "i"(OFF));
-    return r;
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const char* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-
-__device__ __forceinline__ f16x8 cat_tr(s16x4 lo, s16x4 hi) {
-    const auto v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
-
-// KA = 256 (Cout % 256 == 0): a 256x256 tile, 96 MAC per staged byte instead of
-// 64 (KA 128) — the 256x128 body is bound by operand delivery, not the MFMAs
-// (MFMA-busy scales with the intensity: 0.25 at KA 64, 0.42 at KA 128).  Its
-// stage holds PX = 16 pixels (one MFMA k-slice) so three stages fit in 96 KB.
-// The PX = 16 body runs a 4-stage ring (128 KB, inside the epilogue's 132 KB) and
-// issues each stage's DMA as GL = TM pieces placed after the MFMAs of one row
-// (address math branch-free: one wrap per stage, Wo >= PX, see wg_x3_plan), so
-// the per-lane address VALU runs in the MFMA shadow instead of between the
-// barrier and the first MFMA of every stage.
-template <int KA>
-__global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgX3Args a) {
-    constexpr int BR = 256, GX = BR / 32, GD = KA / 32;
-    constexpr int PX = KA == 256 ? 16 : 32;                  // pixels per stage
-    constexpr int NS = PX == 16 ? 4 : 3;                     // LDS ring depth
-    constexpr int ROW = 128, STAGE = (GX + GD) * PX * ROW;
-    constexpr int NX = PX / 8, ND = GD * PX / 64, GL = NX + ND;
-    constexpr int TM = KA / 64, TN = 2;
-    static_assert(ND >= 1 && (KA == 64 || KA == 128 || KA == 256), "KA must be 64, 128 or 256");
-    // the epilogue stages the slab tile (KA x 256 fp32, pitch 264) in passes of
-    // 128 rows through the drained ring: at least 132 KiB
-    constexpr int EPI_ROWS = KA < 128 ? KA : 128, EPI_PITCH = BR + 8;
-    constexpr int LDS = NS * STAGE > EPI_ROWS * EPI_PITCH * 4 ? NS * STAGE : EPI_ROWS * EPI_PITCH * 4;
-    __shared__ __attribute__((aligned(1024))) char smem[LDS];
-
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);       // same pixel range → same XCD
-    const int split = bid / a.tiles, tile = bid - split * a.tiles;
-    const int kt = tile / a.r_tiles, rt = tile - kt * a.r_tiles;
-    const int k0 = kt * KA, r0 = rt * BR;
-    const int p_begin = split * a.mps;
-    const int p_end = min(a.M, p_begin + a.mps);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    // ---- staging bookkeeping ----
-    const int Lx = ((lane & 7) ^ (((lane >> 4) & 1) << 2)) * 8;   // logical chunk (halves) this lane fetches
-    const int mg = r0 + 32 * w;                                   // first column of this wave's x group
-    const bool gvalid = mg < a.RSC;
-    const int tap = gvalid ? mg / a.C : 0;
-    const int cg = gvalid ? (mg - tap * a.C) >> 5 : 0;
-    const int rr = tap / a.S, ss = tap - rr * a.S;
-    const int dh = rr * a.dil - a.pad, dw = ss * a.dil - a.pad;
-    const int xstride = a.C * 2, dstride = a.K * 2;
-    const _Float16* xg = a.xs + cg * 64 + Lx;
-    const _Float16* zero = (const _Float16*)g_x3_zero_line;
-    int xn[NX], xho[NX], xwo[NX];
-    const int hw = a.Ho * a.Wo;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-        const int p = p_begin + 8 * i + (lane >> 3);
-        xn[i] = p / hw;
-        const int rem = p - xn[i] * hw;
-        xho[i] = rem / a.Wo;
-        xwo[i] = rem - xho[i] * a.Wo;
-    }
-    const _Float16* dg[ND];
-    int dpp[ND];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-        const int line = 8 * (w * ND + j) + (lane >> 3);
-        dpp[j] = line % PX;
-        dg[j] = a.dys + (k0 >> 5) * 64 + (line / PX) * 64 + Lx;
-    }
-
-    auto issue = [&](int t) {
-        char* st = smem + (t % NS) * STAGE;
-        const int pb = p_begin + PX * t;
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const int p = pb + 8 * i + (lane >> 3);
-            const int hi = xho[i] * a.stride + dh, wi = xwo[i] * a.stride + dw;
-            const bool in = gvalid && p < p_end && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-            const long pix = ((long)xn[i] * a.H + hi) * a.W + wi;
-            glds16(in ? xg + pix * xstride : zero, st + (w * PX + 8 * i) * ROW);
-            xwo[i] += PX;                                    // this slot's pixel for the next K-step
-            while (xwo[i] >= a.Wo) {
-                xwo[i] -= a.Wo;
-                if (++xho[i] == a.Ho) {
-                    xho[i] = 0;
-                    ++xn[i];
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < ND; ++j) {
-            const int p = pb + dpp[j];
-            glds16(p < p_end ? dg[j] + (long)p * dstride : zero, st + (GX * PX + 8 * (w * ND + j)) * ROW);
-        }
-    };
-
-    // one DMA piece of stage t (PX == 16 body): k < NX an x slot, else a dy slot.
-    // The x slot's pixel advances by PX per stage with at most one row wrap
-    // (Wo >= PX): selects, no branches, so the piece can sit between MFMAs.
-    auto piece = [&](int t, const int k) {
-        char* st = smem + (t & (NS - 1)) * STAGE;
-        const int pb = p_begin + PX * t;
-        // 32-bit byte offsets (wg_x3_plan: both operands < 4 GiB for KA 256), the
-        // validity as a mask and the zero line as a select: no branch
-        if (k < NX) {
-            const int i = k;
-            const int p = pb + 8 * i + (lane >> 3);
-            const int hi = xho[i] * a.stride + dh, wi = xwo[i] * a.stride + dw;
-            const bool in = gvalid & (p < p_end) & ((unsigned)hi < (unsigned)a.H) & ((unsigned)wi < (unsigned)a.W);
-            const unsigned off = (((unsigned)xn[i] * a.H + hi) * a.W + wi) * (unsigned)(xstride * 2);
-            const char* src = in ? (const char*)xg : (const char*)zero;
-            glds16(src + (in ? off : 0u), st + (w * PX + 8 * i) * ROW);
-            const int w2 = xwo[i] + PX;
-            const bool wrap = w2 >= a.Wo;
-            xwo[i] = wrap ? w2 - a.Wo : w2;
-            const int h2 = xho[i] + (wrap ? 1 : 0);
-            const bool wrap2 = h2 == a.Ho;
-            xho[i] = wrap2 ? 0 : h2;
-            xn[i] += wrap2 ? 1 : 0;
-        } else {
-            const int j = k - NX;
-            const int p = pb + dpp[j];
-            const bool in = p < p_end;
-            const char* src = in ? (const char*)dg[j] : (const char*)zero;
-            glds16(src + (in ? (unsigned)p * (unsigned)(dstride * 2) : 0u), st + (GX * PX + 8 * (w * ND + j)) * ROW);
-        }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // transposed-read addressing: 16-lane group G reads 4 pixel rows (q) x 16
-    // channels (column block cb = G&1); lane 4q+p supplies row q, channels 4p..4p+3
-    const int wk = w & 1, wr = w >> 1;
-    const int h = lane >> 5, cb = (lane >> 4) & 1, q = (lane >> 2) & 3, pq = lane & 3;
-    int toff[2];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-        toff[pl] = (8 * h + q) * ROW + (((4 * pl + 2 * cb + (pq >> 1)) ^ (((q >> 1) & 1) << 2)) << 4) + 8 * (pq & 1);
-    const int a_line = (GX + wk * TM) * PX * ROW;     // dy groups of this wave
-    const int b_line = (wr * TN) * PX * ROW;          // x groups of this wave
-
-    struct Frag {
-        f16x8 dh[TM], dl[TM], xh[TN], xl[TN];
-    };
-    // per-lane LDS byte addresses of the two planes' transposed-read blocks
-    const unsigned lds0 = lds_addr_of(smem);
-    const unsigned ta0 = lds0 + a_line + toff[0], ta1 = lds0 + a_line + toff[1];
-    const unsigned tb0 = lds0 + b_line + toff[0], tb1 = lds0 + b_line + toff[1];
-    auto read_frag = [&](Frag& f, int buf, const int s) {
-        const unsigned so = buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            // immediate offsets: tile i (32 rows), half s (16 rows), second read +4 rows
-            if (s == 0) {
-                f.dh[i] = cat_tr(ds_tr16<0>(ta0 + so + i * PX * ROW), ds_tr16<4 * ROW>(ta0 + so + i * PX * ROW));
-                f.dl[i] = cat_tr(ds_tr16<0>(ta1 + so + i * PX * ROW), ds_tr16<4 * ROW>(ta1 + so + i * PX * ROW));
-            } else {
-                f.dh[i] = cat_tr(ds_tr16<16 * ROW>(ta0 + so + i * PX * ROW),
-                                 ds_tr16<20 * ROW>(ta0 + so + i * PX * ROW));
-                f.dl[i] = cat_tr(ds_tr16<16 * ROW>(ta1 + so + i * PX * ROW),
-                                 ds_tr16<20 * ROW>(ta1 + so + i * PX * ROW));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            if (s == 0) {
-                f.xh[j] = cat_tr(ds_tr16<0>(tb0 + so + j * PX * ROW), ds_tr16<4 * ROW>(tb0 + so + j * PX * ROW));
-                f.xl[j] = cat_tr(ds_tr16<0>(tb1 + so + j * PX * ROW), ds_tr16<4 * ROW>(tb1 + so + j * PX * ROW));
-            } else {
-                f.xh[j] = cat_tr(ds_tr16<16 * ROW>(tb0 + so + j * PX * ROW),
-                                 ds_tr16<20 * ROW>(tb0 + so + j * PX * ROW));
-                f.xl[j] = cat_tr(ds_tr16<16 * ROW>(tb1 + so + j * PX * ROW),
-                                 ds_tr16<20 * ROW>(tb1 + so + j * PX * ROW));
-            }
-        }
-    };
-    auto mma = [&](const Frag& f) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.dh[i], f.xh[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.dh[i], f.xl[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.dl[i], f.xh[j], acc[i][j], 0, 0, 0);
-            }
-    };
-    // same software pipeline as conv_x3_kernel<*, 2> (see there); 4*(TM+TN)
-    // transposed b64 reads per half, two per MFMA gap.  The reads are inline
-    // asm: every consumer MFMA sits behind an explicit lgkmcnt wait + sched_barrier.
-    constexpr int NR = 4 * (TM + TN), NM = 3 * TM * TN;
-    const int nsteps = p_end > p_begin ? (p_end - p_begin + PX - 1) / PX : 0;
-    if constexpr (PX == 16) {
-        // one dy fragment set, refilled row by row right after its MFMAs issue
-        // (128 accumulators + 32 dy + 2x16 x registers): per stage t
-        // [wait own DMA t+1 and this wave's reads, barrier | t+1's x fragments |
-        //  rows i = 0..TM-1: t's MFMAs, one DMA piece of stage t+3, t+1's row i]
-        struct XF {
-            f16x8 xh[TN], xl[TN];
-        };
-        f16x8 dh[TM], dl[TM];
-        XF x0, x1;
-        auto read_d = [&](const int i, const unsigned so) {
-            dh[i] = cat_tr(ds_tr16<0>(ta0 + so + i * PX * ROW), ds_tr16<4 * ROW>(ta0 + so + i * PX * ROW));
-            dl[i] = cat_tr(ds_tr16<0>(ta1 + so + i * PX * ROW), ds_tr16<4 * ROW>(ta1 + so + i * PX * ROW));
-        };
-        auto read_x = [&](XF& x, const unsigned so) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                x.xh[j] = cat_tr(ds_tr16<0>(tb0 + so + j * PX * ROW), ds_tr16<4 * ROW>(tb0 + so + j * PX * ROW));
-                x.xl[j] = cat_tr(ds_tr16<0>(tb1 + so + j * PX * ROW), ds_tr16<4 * ROW>(tb1 + so + j * PX * ROW));
-            }
-        };
-        auto mma_row = [&](const int i, const XF& x) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh[i], x.xh[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh[i], x.xl[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dl[i], x.xh[j], acc[i][j], 0, 0, 0);
-            }
-        };
-        static_assert(PX != 16 || GL == TM, "one DMA piece per MFMA row");
-        if (nsteps > 0) {
-            // prologue: stages 0..NS-2 (past the end: zero lines, never read)
-#pragma unroll
-            for (int u = 0; u < NS - 1; ++u)
-#pragma unroll
-                for (int k = 0; k < GL; ++k) piece(u, k);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * GL) : "memory");
-            lds_barrier();
-            read_x(x0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) read_d(i, 0);
-            // step t: wait for stage t+1 (stage t+2's pieces stay in flight), barrier,
-            // read t+1's fragments row by row beside t's MFMAs, and issue stage
-            // t+3's pieces (into the buffer stage t-1 used: every wave finished
-            // reading it before this step's barrier) one per MFMA row.  Stages past
-            // the end load zero lines into buffers no later stage reads, so every
-            // non-final step is the same branch-free code.
-            auto step = [&](const int t, const XF& xa, XF& xb) {
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NS - 3) * GL) : "memory");
-                lds_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned so = ((t + 1) & (NS - 1)) * STAGE;
-                read_x(xb, so);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    mma_row(i, xa);
-                    piece(t + NS - 1, i);
-                    read_d(i, so);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            auto last = [&](const XF& xa) {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // + the dummy DMAs
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) mma_row(i, xa);
-            };
-            int t = 0;
-            for (; t + 2 < nsteps; t += 2) {
-                step(t, x0, x1);
-                step(t + 1, x1, x0);
-            }
-            // the x fragments' reads retire before the join's register copies read
-            // them (asm reads are untracked; tools/trcheck.py)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 1 < nsteps) {
-                step(t, x0, x1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                x0 = x1;                                     // one last() call site
-            }
-            last(x0);
-        }
-    } else if (nsteps > 0) {
-        int q_t = 0;
-        auto issue_next = [&]() { issue(q_t++); };
-        issue_next();
-        if (nsteps > 1) issue_next();
-        if (nsteps > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lds_barrier();
-        Frag f0, f1;
-        int cur = 0;
-        read_frag(f0, 0, 0);
-        auto step = [&](const bool ISSUE, const bool NEXT) {
-            const int bcur = cur;
-            if (ISSUE) issue_next();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // f0 (read last half) landed
-            __builtin_amdgcn_sched_barrier(0);
-            read_frag(f1, bcur, 1);
-            mma(f0);
-#pragma unroll
-            for (int k = 0; k < NR / 2; ++k) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x001, 2, 0);   // the asm reads count as ALU
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, NM - NR / 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (NEXT) {
-                if (ISSUE) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GL) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                lds_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                cur = cur == 2 ? 0 : cur + 1;
-                mma(f1);
-                read_frag(f0, cur, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                for (int k = 0; k < NR / 2; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x001, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, NM - 1 - NR / 2, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                mma(f1);
-            }
-        };
-        int t = 0;
-        for (; t + 2 < nsteps; ++t) step(true, true);
-        if (t + 1 < nsteps) {
-            step(false, true);
-            ++t;
-        }
-        step(false, false);
-    }
-
-    // ---- epilogue: the slab tile staged through the drained ring in passes of
-    // EPI_ROWS output-channel rows and written as 16-B row chunks (whole 128-B
-    // lines, 32-64 stores per thread).  Per-element stores from the fragments
-    // (128 per thread, past a wave's 63 outstanding memory ops) stalled every
-    // wave on their completion while all CUs wrote their slabs at once.
-    const float inv = 1.f / pow2_scale_for(a.amax);
-    float* out = a.ws + (long)split * a.K * a.RSC;
-    float* t = (float*)smem;
-    constexpr int PASSES = KA / EPI_ROWS, C4 = BR / 4;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    lds_barrier();                                             // every wave done with the ring
-#pragma unroll
-    for (int ps = 0; ps < PASSES; ++ps) {
-        // wave rows: k_local = wk*TM*32 + i*32 + 8*(r>>2) + 4*h + (r&3) in [ps*EPI_ROWS, +EPI_ROWS)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int kb = wk * TM * 32 + i * 32;
-            if (kb / EPI_ROWS != ps) continue;                 // wave-uniform
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    t[(kb - ps * EPI_ROWS + 8 * (r >> 2) + 4 * h + (r & 3)) * EPI_PITCH + wr * 64 + j * 32 + (lane & 31)] =
-                        acc[i][j][r] * inv;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        lds_barrier();
-        const int mcols = min(BR, a.RSC - r0);                 // multiple of 4 (RSC = R*S*C, C % 32 == 0)
-#pragma unroll 4
-        for (int e = tid; e < EPI_ROWS * C4; e += 512) {
-            const int row = e / C4, c4 = e - row * C4;
-            if (c4 * 4 < mcols)
-                *(f32x4*)(out + (long)(k0 + ps * EPI_ROWS + row) * a.RSC + r0 + c4 * 4) =
-                    *(const f32x4*)(t + row * EPI_PITCH + c4 * 4);
-        }
-        if (ps + 1 < PASSES) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lds_barrier();
-        }
-    }
-}
-
-// Weight gradient of a 3x3, stride-1, pad-1, dilation-1 conv from one staged halo
-// (round 6; the small-channel layers).  The tiled body above stages a pixel's x
-// line once per 256-column group — for C = 64 three groups, the third 1/4 used —
-// so its K-step moves 40 KiB per 64x256 tile and runs at MFMA busy 0.25.  Here a
-// block owns 64 output channels x all 9 taps x 64 input channels (576 slab
-// columns); a K-step is one patch of 4 output rows x 16 columns (Ho % 4 == 0,
-// Wo % 16 == 0), staged as its 6 x 18 input halo x 2 channel groups (every tap
-// of every row of the patch reads from it) beside the patch's dy lines: 43 KiB
-// for 64 pixels.  16x16x32 MFMAs over two 32-pixel k-slices (patch rows 0-1,
-// 2-3): wave w owns K rows 32*(w&1).. (2 m-tiles) x input channels 16*(w>>1)..
-// of every tap (9 n-tiles, 72 accumulators); the x fragment of tap (r, s) for
-// patch row i is staged row i + r read s lines further.  Both operands come from
-// ds_read_b64_tr_b16 (8 consecutive pixels of one channel per lane).  Swizzle:
-// 16-B chunk ^= 2*(((j>>1)&1) | ((j>>3)&1)<<1) for line j of a run, so the 8
-// lines a 32-lane half of a transposed read touches ({a..a+3} u {a+8..a+11}, any
-// shift a) fall on 8 distinct 32-B bank slots.  3-stage ring, one barrier per
-// K-step; slabs [split][K][R*S*C] as wgrad_x3_kernel's (same reduce), the pixel
-// ranges whole patches.
-constexpr int WGH_LX = 18, WGH_XL = 12 * WGH_LX, WGH_SL = WGH_XL + 128, WGH_STAGE = WGH_SL * 128, WGH_NS = 3;
-constexpr int WGH_PITCH = 580;                       // epilogue rows: 576 slab columns + 4 (conflict-free stores)
-// s_waitcnt lgkmcnt(N) for a compile-time N (after unrolling)
-__device__ __forceinline__ void wait_lgkm(const int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory"); break;
-    }
-}
-__global__ __launch_bounds__(512, 1) void wgrad_x3_halo_kernel(WgX3Args a) {
-    constexpr int ROW = 128, LX = WGH_LX, XL = WGH_XL, STAGE = WGH_STAGE, NS = WGH_NS;
-    // DMA pieces per stage: XP x pieces as slots 0-3 of the 8 waves (piece w + 8 i;
-    // past XP the sink), the 16 dy pieces as slots 4-5 (piece w + 8 (i - 4))
-    constexpr int XP = XL / 8, XS = 4, SLOTS = XS + 2;
-    static_assert(XP <= 8 * XS, "x pieces");
-    constexpr int SINK = NS * STAGE;
-    static_assert(XL % 8 == 0 && 32 * WGH_PITCH * 4 <= SINK, "wgrad halo LDS");
-    __shared__ __attribute__((aligned(1024))) char smem[SINK + 1024];
-
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);       // same pixel range → same XCD
-    const int split = bid / a.tiles, tile = bid - split * a.tiles;
-    const int kt = tile / a.r_tiles, ct = tile - kt * a.r_tiles;
-    const int k0 = kt * 64, c0 = ct * 64;
-    const int HP = a.Ho / 4, WP = a.Wo / 16, npatch = a.N * HP * WP;
-    const int P0 = split * a.mps;                            // this split's patches [P0, P1)
-    const int P1 = min(npatch, P0 + a.mps);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    auto xsw = [](int j) { return (((j >> 1) & 1) | (((j >> 3) & 1) << 1)) << 1; };
-
-    // ---- DMA sources: raw-buffer loads (an offset past num_records loads zeros:
-    // halo lines outside the image, patches past the range, the sink pieces; the
-    // operands are under 2 GiB, wg_halo_shape, so bit 31 marks them).  Stride 1,
-    // pad 1: input pixel of halo line (staged row R, column j) of the patch at
-    // output pixel p (its top-left) is p + (R - 1) W + j - 1, so a lane's byte
-    // offset is the stage's p * 4C plus a constant ----
-    const i32x4 xr = buffer_rsrc(a.xs, (unsigned)((long)a.N * a.H * a.W * a.C * 4));
-    const i32x4 dr = buffer_rsrc(a.dys, (unsigned)((long)a.M * a.K * 4));
-    int xk[XS];                 // byte offset from the stage's p * 4C (signed)
-    int xg[XS];                 // halo edge of the line: top row | bottom row << 1 | left column << 2 | right << 3
-#pragma unroll
-    for (int i = 0; i < XS; ++i) {
-        const int pc = min(w + 8 * i, XP - 1);               // past XP: a valid line, loaded into the sink
-        const int L = 8 * pc + (lane >> 3), run = L / LX, j = L - run * LX;
-        const int R = run >> 1, cg = run & 1;
-        xk[i] = ((R - 1) * a.W + j - 1) * (a.C * 4) + ((c0 / 32 + cg) * 64 + ((lane & 7) ^ xsw(j)) * 8) * 2;
-        xg[i] = (R == 0 ? 1 : 0) | (R == 5 ? 2 : 0) | (j == 0 ? 4 : 0) | (j == LX - 1 ? 8 : 0);
-    }
-    int dk[2];                  // dy: byte offset from the stage's p * 4K (line: K group | patch row | column)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int L = 8 * (w + 8 * i) + (lane >> 3), pr = (L >> 4) & 3, cc = L & 15;
-        dk[i] = (pr * a.W + cc) * (a.K * 4) + ((k0 / 32 + (L >> 6)) * 64 + ((lane & 7) ^ xsw(L & 31)) * 8) * 2;
-    }
-    // the patch being issued: index, top-left output pixel, patch row / column (wave-uniform)
-    int q_P = P0, q_hp, q_wp, q_p;
-    {
-        const int n = P0 / (HP * WP), rem = P0 - n * (HP * WP);
-        q_hp = rem / WP;
-        q_wp = rem - q_hp * WP;
-        q_p = (n * a.Ho + 4 * q_hp) * a.Wo + 16 * q_wp;
-    }
-    int q_t = 0, q_em = 0, q_bad = 0;
-    auto begin_issue = [&]() {
-        q_em = (q_hp == 0 ? 1 : 0) | (q_hp == HP - 1 ? 2 : 0) | (q_wp == 0 ? 4 : 0) | (q_wp == WP - 1 ? 8 : 0);
-        q_bad = q_P >= P1 ? 1 : 0;
-    };
-    auto piece = [&](const int i) {
-        char* st = smem + (q_t % NS) * STAGE;
-        if (i < XS) {
-            // branch-free: an invalid line gets bit 31 (past num_records) or'd in
-            const int pc = w + 8 * i;                        // wave-uniform
-            const unsigned bad = (unsigned)q_bad | (unsigned)((xg[i] & q_em) != 0) | (unsigned)(pc >= XP);
-            blds16(xr, (unsigned)(q_p * (a.C * 4) + xk[i]) | (bad << 31), 0, pc < XP ? st + pc * 1024 : smem + SINK);
-        } else {
-            blds16(dr, (unsigned)(q_p * (a.K * 4) + dk[i - XS]) | ((unsigned)q_bad << 31), 0,
-                   st + XL * ROW + (w + 8 * (i - XS)) * 1024);
-        }
-    };
-    auto end_issue = [&]() {                                 // the next patch
-        ++q_t;
-        ++q_P;
-        q_p += 16;
-        if (++q_wp == WP) {
-            q_wp = 0;
-            q_p += 3 * a.Wo;
-            q_hp = q_hp + 1 == HP ? 0 : q_hp + 1;
-        }
-    };
-    auto issue = [&]() {
-        begin_issue();
-#pragma unroll
-        for (int i = 0; i < SLOTS; ++i) piece(i);
-        end_issue();
-    };
-
-    f32x4 acc[2][9];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // ---- transposed-read addresses (stage-relative bytes, k-slice 0): 16-lane
-    // group G reads patch row G >> 1 (+2 in k-slice 1), pixels 8 (G & 1) + q (+4 the
-    // second read) of 16 channels; lane 4q + pp supplies row q, channels 4pp..4pp+3 ----
-    const int G = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    const int kh = w & 1, cb4 = w >> 1, cg = cb4 >> 1, cbl = cb4 & 1;
-    unsigned a_ad[2][2];        // dy: [m-tile][plane]; line 8G + q of the wave's K group (+4: same swizzle)
-    {
-        const int j = 8 * G + q;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-                a_ad[mi][pl] = (unsigned)((XL + 64 * kh + j) * ROW + ((((pl * 4 + mi * 2 + (pp >> 1)) ^ xsw(j))) << 4) +
-                                          8 * (pp & 1));
-    }
-    unsigned b_ad[3][2][2];     // x: [tap column s][read half][plane], staged row G >> 1 (+ k-slice * 2 + r)
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int j = 8 * (G & 1) + q + s + 4 * h2;
-            const int run = (G >> 1) * 2 + cg;
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-                b_ad[s][h2][pl] = (unsigned)((run * LX + j) * ROW + ((((pl * 4 + cbl * 2 + (pp >> 1)) ^ xsw(j))) << 4) +
-                                             8 * (pp & 1));
-        }
-    const unsigned lds0 = lds_addr_of(smem);
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) a_ad[mi][pl] += lds0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) b_ad[s][h2][pl] += lds0;
-
-    // Per K-step t (stage t in LDS): 18 tap-slices v = 9 * k-slice + tap, each's x
-    // fragments read two ahead, k-slice 1's dy fragments in two halves at v = 3 and
-    // 6; after v = 15 the step's one barrier (stage t+1 landed everywhere, stage
-    // t-1 read by everyone), then stage t+1's k-slice-0 dy and first x fragments
-    // read beside v = 16-17, and stage t+NS-1's DMA pieces (into stage t-1's
-    // buffer) issued between them — the barrier and the next stage's first LDS
-    // latency sit behind this wave's own MFMAs.  lgkmcnt counts this wave's
-    // transposed reads in issue order (at most 15 outstanding: waits of 8 and 12).
-    // A step with no stage after it reads none (an asm read whose result is never
-    // used leaves its registers free to the compiler while it is in flight).
-    const int nsteps = P1 - P0;
-    f16x8 dfa[2][2], dfb[2][2], xfr[3][2];
-    auto read_d = [&](f16x8 (&d)[2][2], const int mi, const unsigned so) {
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-            d[mi][pl] = cat_tr(ds_tr16<0>(a_ad[mi][pl] + so), ds_tr16<4 * ROW>(a_ad[mi][pl] + so));
-    };
-    auto read_x = [&](const int v, const unsigned so) {
-        const int kk = v / 9, tap = v - 9 * (v / 9), r = tap / 3, s = tap - 3 * (tap / 3);
-        const unsigned ro = so + (unsigned)((2 * kk + r) * 2 * LX * ROW);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-            xfr[v % 3][pl] = cat_tr(ds_tr16<0>(b_ad[s][0][pl] + ro), ds_tr16<0>(b_ad[s][1][pl] + ro));
-    };
-    auto mfma_v = [&](const f16x8 (&d)[2][2], const int v) {
-        const int tap = v % 9;
-        const f16x8* xf = xfr[v % 3];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            acc[mi][tap] = __builtin_amdgcn_mfma_f32_16x16x32_f16(d[mi][0], xf[0], acc[mi][tap], 0, 0, 0);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            acc[mi][tap] = __builtin_amdgcn_mfma_f32_16x16x32_f16(d[mi][0], xf[1], acc[mi][tap], 0, 0, 0);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            acc[mi][tap] = __builtin_amdgcn_mfma_f32_16x16x32_f16(d[mi][1], xf[0], acc[mi][tap], 0, 0, 0);
-    };
-    if (nsteps > 0) {
-#pragma unroll
-        for (int u = 0; u < NS - 1; ++u) issue();           // stages past the end: zero lines, never read
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * SLOTS) : "memory");
-        lds_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        read_d(dfa, 0, 0u);
-        read_d(dfa, 1, 0u);
-        read_x(0, 0u);
-        read_x(1, 0u);
-        unsigned so = 0;
-        auto step = [&](const bool next) {
-            const unsigned sn = so == (unsigned)((NS - 1) * STAGE) ? 0u : so + STAGE;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                read_x(v + 2, so);
-                if (v == 3) read_d(dfb, 0, so + 32 * ROW);
-                if (v == 6) read_d(dfb, 1, so + 32 * ROW);
-                wait_lgkm(v >= 3 && v <= 8 ? 12 : 8);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_v(v < 9 ? dfa : dfb, v);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 3) * SLOTS) : "memory");   // stage t+1
-            lds_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            if (next) {
-                read_d(dfa, 0, sn);
-                read_d(dfa, 1, sn);
-                wait_lgkm(12);                                          // x of v = 16
-            } else {
-                wait_lgkm(4);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_v(dfb, 16);
-            __builtin_amdgcn_sched_barrier(0);
-            if (next) read_x(0, sn);
-            begin_issue();
-            piece(0);
-            piece(1);
-            piece(2);
-            wait_lgkm(next ? 12 : 0);                                   // x of v = 17
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_v(dfb, 17);
-            __builtin_amdgcn_sched_barrier(0);
-            if (next) read_x(1, sn);
-#pragma unroll
-            for (int i = 3; i < SLOTS; ++i) piece(i);
-            end_issue();
-            __builtin_amdgcn_sched_barrier(0);
-            so = sn;
-        };
-        for (int t = 0; t + 1 < nsteps; ++t) step(true);
-        step(false);
-    }
-
-    // ---- epilogue: the 64 x 576 slab tile through the drained ring in two passes
-    // of 32 K rows (one per wave row), stored as 16-B row chunks ----
-    const float inv = 1.f / pow2_scale_for(a.amax);
-    float* out = a.ws + (long)split * a.K * a.RSC;
-    float* T = (float*)smem;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // + the DMAs past the end
-    lds_barrier();
-#pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-        if (kh == ps) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        T[(16 * mi + 4 * G + e) * WGH_PITCH + tap * 64 + 16 * cb4 + (lane & 15)] = acc[mi][tap][e] * inv;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        lds_barrier();
-        for (int e = tid; e < 32 * 144; e += 512) {
-            const int row = e / 144, c4 = e - row * 144, tap = c4 >> 4, cc = (c4 & 15) * 4;
-            *(f32x4*)(out + (long)(k0 + 32 * ps + row) * a.RSC + tap * a.C + c0 + cc) =
-                *(const f32x4*)(T + row * WGH_PITCH + tap * 64 + cc);
-        }
-        if (ps == 0) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lds_barrier();
-        }
-    }
-}
-
-// dw[i] = sum_split ws[split][i], fixed order
-// Sum of the split-K slabs [splits][n4] (fixed order, deterministic).  G = 1: a
-// thread per float4 element, its slabs summed left to right with 16 loads in
-// flight; G = 4 (8 loads in flight per thread) (many splits: the small layers' wgrads split over up to ~75
-// pixel ranges): the four waves of a block take the same 64 elements, wave g
-// summing slabs g, g+4, g+8, ... left to right, and the four partial sums are
-// added in wave order through LDS — 4x fewer dependent load round trips per
-// element.
-template <int G>
-__global__ __launch_bounds__(256) void wg_x3_reduce_kernel(long n4, int splits, const f32x4* __restrict__ ws,
-                                                          f32x4* __restrict__ dw) {
-    constexpr int B = G == 1 ? 16 : 8;      // slab loads in flight per thread
-    auto sum_from = [&](long i, int k0, int step) {
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        bool first = true;
-        for (int k = k0; k < splits; k += B * step) {
-            f32x4 v[B];
-#pragma unroll
-            for (int u = 0; u < B; ++u)
-                if (k + u * step < splits) v[u] = __builtin_nontemporal_load(&ws[(long)(k + u * step) * n4 + i]);
-#pragma unroll
-            for (int u = 0; u < B; ++u)
-                if (k + u * step < splits) {
-                    if (first) s = v[u];
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) s[e] += v[u][e];
-                    first = false;
-                }
-        }
-        return s;
-    };
-    if constexpr (G == 1) {
-        const long stride = (long)gridDim.x * blockDim.x;
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) dw[i] = sum_from(i, 0, 1);
-    } else {
-        static_assert(G == 4, "wg_x3_reduce_kernel: G is 1 or 4");
-        __shared__ f32x4 part[G][64];
-        const int g = threadIdx.x >> 6, l = threadIdx.x & 63;
-        for (long b0 = (long)blockIdx.x * 64; b0 < n4; b0 += (long)gridDim.x * 64) {
-            const long i = b0 + l;
-            if (i < n4 && g < splits) part[g][l] = sum_from(i, g, G);
-            __syncthreads();
-            if (g == 0 && i < n4) {
-                f32x4 s = part[0][l];
-                for (int q = 1; q < G && q < splits; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) s[e] += part[q][l][e];
-                dw[i] = s;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-
-// Stem operand: the image → zero-padded NHWC4 planes [2][N][Hp][Wp][4] (hi, then
-// lo = f16(x-hi)); padded pixel (hp, wp) = input (hp-3, wp-3).  U8: the image is
-// the uint8 HWC batch cv2.imread gives ([N][H][W][C], BGR) and x = u8 / 255 in
-// fp32 — ToTensor (dataset.py:16) fused into the stem's operand pack.
-template <bool U8>
-__global__ __launch_bounds__(256) void stem_pack_x3_kernel(int N, int C, int H, int W, int Hp, int Wp,
-                                                          const void* __restrict__ src, _Float16* __restrict__ out) {
-    const long total = (long)N * Hp * Wp;
-    const long plane = total * 4;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) {
-        const int wp = (int)(p % Wp);
-        const long t = p / Wp;
-        const int hp = (int)(t % Hp);
-        const int n = (int)(t / Hp);
-        const int h = hp - 3, w = wp - 3;
-        const bool in = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-        f32x4 v;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (!(in && c < C)) {
-                v[c] = 0.f;
-            } else if constexpr (U8) {
-                const uint8_t u = ((const uint8_t*)src)[(((long)n * H + h) * W + w) * C + c];
-                v[c] = __fdiv_rn((float)u, 255.f);
-            } else {
-                v[c] = ((const float*)src)[(((long)n * C + c) * H + h) * W + w];
-            }
-        }
-        h16x4 hv, lv;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const _Float16 hh = (_Float16)v[c];
-            hv[c] = hh;
-            lv[c] = (_Float16)(v[c] - (float)hh);
-        }
-        *(h16x4*)(out + p * 4) = hv;
-        *(h16x4*)(out + plane + p * 4) = lv;
-    }
-}
-
-// Stem weight OIHW [K][C][7][7] * 2^e_k → [K][r][hi32|lo32], 32 = 8 taps (s; 7 = 0)
-// x 4 channels (C..3 = 0); one block per k, wscale[k] = 2^-e_k
-__global__ __launch_bounds__(256) void stem_weight_pack_x3_kernel(int C, const float* __restrict__ w,
-                                                                 _Float16* __restrict__ out,
-                                                                 float* __restrict__ wscale) {
-    const int k = blockIdx.x;
-    const float* wk = w + (long)k * C * 49;
-    const float sc = pow2_scale_of(block_absmax(C * 49, [&](int i) { return wk[i]; }));
-    for (int e = threadIdx.x; e < 7 * 32; e += blockDim.x) {
-        const int c = e & 3, s = (e >> 2) & 7, r = e >> 5;
-        const float v = (s < 7 && c < C) ? wk[(c * 7 + r) * 7 + s] * sc : 0.f;
-        split_store(v, out + ((long)k * 7 + r) * 64 + s * 4 + c);
-    }
-    if (threadIdx.x == 0) wscale[k] = 1.f / sc;
-}
+namespace hkp {
 
 // Compute units (one 512-thread conv block per CU at a time); cached per process.
 static int x3_cus() {
@@ -3559,25 +1640,6 @@ static void launch_x3(const X3Problem& p, const X3LaunchPlan& pl, hipStream_t st
 
 using namespace hkp;
 
-extern "C" int hkp_weight_pack_x3(int32_t k, int32_t rsc, int32_t c, const float* w, uint16_t* w_split,
-                                  float* w_inv_scale, hkp_stream_t stream) {
-    HKP_CHECK_ARG(k > 0 && c > 0 && c % 32 == 0 && rsc > 0 && rsc % c == 0 && w && w_split && w_inv_scale,
-                  "hkp_weight_pack_x3: bad args");
-    hipLaunchKernelGGL(weight_pack_x3_kernel, dim3(k), dim3(256), 0, as_stream(stream), rsc, w, (_Float16*)w_split,
-                       w_inv_scale);
-    HKP_LAUNCH_CHECK("hkp_weight_pack_x3");
-    return HKP_OK;
-}
-
-extern "C" int hkp_weight_pack_f16(int32_t k, int32_t rsc, const float* w, uint16_t* w_f16, float* w_inv_scale,
-                                   hkp_stream_t stream) {
-    HKP_CHECK_ARG(k > 0 && rsc > 0 && w && w_f16 && w_inv_scale, "hkp_weight_pack_f16: bad args");
-    hipLaunchKernelGGL(weight_pack_f16_kernel, dim3(k), dim3(256), 0, as_stream(stream), rsc, w, (_Float16*)w_f16,
-                       w_inv_scale);
-    HKP_LAUNCH_CHECK("hkp_weight_pack_f16");
-    return HKP_OK;
-}
-
 extern "C" int64_t hkp_conv_x3_sk_workspace_bytes(void) { return x3_sk_ws_bytes(256, x3_cus()); }
 
 static int check_tile(const hkp_conv_desc* d, const char* who) {
@@ -3693,27 +1755,6 @@ extern "C" int hkp_conv2d_fwd_f16_bn(const hkp_conv_desc* d, const uint16_t* x_f
                               stream, "hkp_conv2d_fwd_f16_bn", &ep);
 }
 
-extern "C" int hkp_split_pack_x3(int64_t n, int32_t c, const float* x, const uint32_t* amax_bits,
-                                 uint16_t* x_split, hkp_stream_t stream) {
-    HKP_CHECK_ARG(n > 0 && c > 0 && c % 32 == 0 && n % c == 0 && x && x_split, "hkp_split_pack_x3: bad args");
-    long g = (n / 4 + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(split_pack_x3_kernel, dim3((unsigned)g), dim3(256), 0, as_stream(stream), (long)(n / 4),
-                       (const f32x4*)x, (const unsigned*)amax_bits, (_Float16*)x_split);
-    HKP_LAUNCH_CHECK("hkp_split_pack_x3");
-    return HKP_OK;
-}
-
-extern "C" int hkp_weight_flip_pack_x3(const hkp_conv_desc* d, const float* w, uint16_t* wf_split,
-                                       float* wf_inv_scale, hkp_stream_t stream) {
-    HKP_CHECK_ARG(d && w && wf_split && wf_inv_scale, "hkp_weight_flip_pack_x3: null argument");
-    HKP_CHECK_ARG(d->k % 32 == 0, "hkp_weight_flip_pack_x3: need Cout%%32==0 (k=%d)", d->k);
-    hipLaunchKernelGGL(weight_flip_pack_x3_kernel, dim3(d->c), dim3(256), 0, as_stream(stream), d->k, d->r, d->s,
-                       d->c, w, (_Float16*)wf_split, wf_inv_scale);
-    HKP_LAUNCH_CHECK("hkp_weight_flip_pack_x3");
-    return HKP_OK;
-}
-
 extern "C" int hkp_conv2d_bwd_data_x3(const hkp_conv_desc* d, const uint16_t* dy_split, const uint16_t* wf_split,
                                       const float* wf_inv_scale, const uint32_t* dy_amax_bits, const float* add,
                                       float* dx, void* sk_workspace, int64_t sk_ws_bytes, hkp_stream_t stream) {
@@ -3804,103 +1845,6 @@ extern "C" int hkp_conv2d_bwd_data_x3_strided(const hkp_conv_desc* d, const uint
             launch_x3(p, x3_plan_of(p, d->tile, sk_workspace, sk_ws_bytes), st, a, sk_workspace);
             HKP_LAUNCH_CHECK("hkp_conv2d_bwd_data_x3_strided");
         }
-    return HKP_OK;
-}
-
-extern "C" int64_t hkp_conv_bwd_filter_x3_workspace(const hkp_conv_desc* d) {
-    int ho, wo;
-    if (hkp_conv_out_hw(d, &ho, &wo) != HKP_OK) return -1;
-    int sp, mps, ka, rt;
-    wg_x3_plan(d, (long)d->n * ho * wo, wo, &sp, &mps, &ka, &rt);
-    return (int64_t)sp * d->k * d->r * d->s * d->c * (int64_t)sizeof(float);
-}
-
-extern "C" int hkp_conv2d_bwd_filter_x3(const hkp_conv_desc* d, const uint16_t* x_split, const uint16_t* dy_split,
-                                        const uint32_t* dy_amax_bits, float* dw, void* workspace, int64_t ws_bytes,
-                                        hkp_stream_t stream) {
-    int ho, wo;
-    int rc = hkp_conv_out_hw(d, &ho, &wo);
-    if (rc) return rc;
-    HKP_CHECK_ARG(x_split && dy_split && dw && workspace, "hkp_conv2d_bwd_filter_x3: null tensor");
-    HKP_CHECK_ARG(d->in_layout == HKP_LAYOUT_NHWC, "hkp_conv2d_bwd_filter_x3: NHWC convs only");
-    HKP_CHECK_ARG(d->k % 64 == 0 && d->c % 32 == 0, "hkp_conv2d_bwd_filter_x3: need Cout%%64==0, Cin%%32==0");
-    const long M = (long)d->n * ho * wo;
-    HKP_CHECK_ARG(M < (1L << 31), "hkp_conv2d_bwd_filter_x3: too large");
-    int sp, mps, ka, rt;
-    wg_x3_plan(d, M, wo, &sp, &mps, &ka, &rt);
-    const long n = (long)d->k * d->r * d->s * d->c;
-    HKP_CHECK_ARG(ws_bytes >= sp * n * (long)sizeof(float), "hkp_conv2d_bwd_filter_x3: workspace %ld < %ld",
-                  (long)ws_bytes, sp * n * (long)sizeof(float));
-    WgX3Args a;
-    a.xs = (const _Float16*)x_split; a.dys = (const _Float16*)dy_split; a.amax = (const unsigned*)dy_amax_bits;
-    a.ws = (float*)workspace;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.C = d->c; a.K = d->k; a.R = d->r; a.S = d->s;
-    a.stride = d->stride; a.pad = d->pad; a.dil = d->dilation; a.Ho = ho; a.Wo = wo;
-    a.M = (int)M; a.RSC = d->r * d->s * d->c; a.r_tiles = rt; a.mps = mps;
-    a.tiles = (d->k / (ka ? ka : 64)) * rt;
-    hipStream_t st = as_stream(stream);
-    const unsigned grid = (unsigned)(a.tiles * sp);
-    if (ka == 0) hipLaunchKernelGGL(wgrad_x3_halo_kernel, dim3(grid), dim3(512), 0, st, a);
-    else if (ka == 256) hipLaunchKernelGGL(wgrad_x3_kernel<256>, dim3(grid), dim3(512), 0, st, a);
-    else if (ka == 128) hipLaunchKernelGGL(wgrad_x3_kernel<128>, dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(wgrad_x3_kernel<64>, dim3(grid), dim3(512), 0, st, a);
-    HKP_LAUNCH_CHECK("hkp_conv2d_bwd_filter_x3");
-    if (sp > 16) {
-        long g = (n / 4 + 63) / 64;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(wg_x3_reduce_kernel<4>, dim3((unsigned)g), dim3(256), 0, st, n / 4, sp,
-                           (const f32x4*)workspace, (f32x4*)dw);
-    } else {
-        long g = (n / 4 + 255) / 256;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(wg_x3_reduce_kernel<1>, dim3((unsigned)g), dim3(256), 0, st, n / 4, sp,
-                           (const f32x4*)workspace, (f32x4*)dw);
-    }
-    HKP_LAUNCH_CHECK("hkp_conv2d_bwd_filter_x3 (reduce)");
-    return HKP_OK;
-}
-
-extern "C" int64_t hkp_stem_pack_x3_elems(const hkp_conv_desc* d) {
-    int ho, wo;
-    if (!stem_x3_shape(d) || hkp_conv_out_hw(d, &ho, &wo) != HKP_OK) return -1;
-    return 2L * d->n * (2L * ho + 6) * (2L * wo + 6) * 4;
-}
-
-static int stem_pack(const hkp_conv_desc* d, const void* src, bool u8, uint16_t* x_split, hkp_stream_t stream,
-                     const char* who) {
-    int ho, wo;
-    int rc = hkp_conv_out_hw(d, &ho, &wo);
-    if (rc) return rc;
-    HKP_CHECK_ARG(stem_x3_shape(d), "%s: needs the 7x7/s2/p3 NCHW stem with C<=4, Cout%%64==0", who);
-    HKP_CHECK_ARG(src && x_split, "%s: null tensor", who);
-    const int hp = 2 * ho + 6, wp = 2 * wo + 6;
-    long g = ((long)d->n * hp * wp + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (u8)
-        hipLaunchKernelGGL(stem_pack_x3_kernel<true>, dim3((unsigned)g), dim3(256), 0, as_stream(stream), d->n, d->c,
-                           d->h, d->w, hp, wp, src, (_Float16*)x_split);
-    else
-        hipLaunchKernelGGL(stem_pack_x3_kernel<false>, dim3((unsigned)g), dim3(256), 0, as_stream(stream), d->n, d->c,
-                           d->h, d->w, hp, wp, src, (_Float16*)x_split);
-    HKP_LAUNCH_CHECK(who);
-    return HKP_OK;
-}
-
-extern "C" int hkp_stem_pack_x3(const hkp_conv_desc* d, const float* x_nchw, uint16_t* x_split, hkp_stream_t stream) {
-    return stem_pack(d, x_nchw, false, x_split, stream, "hkp_stem_pack_x3");
-}
-
-extern "C" int hkp_stem_pack_x3_u8(const hkp_conv_desc* d, const uint8_t* img_nhwc, uint16_t* x_split,
-                                   hkp_stream_t stream) {
-    return stem_pack(d, img_nhwc, true, x_split, stream, "hkp_stem_pack_x3_u8");
-}
-
-extern "C" int hkp_stem_weight_pack_x3(int32_t k, int32_t c, const float* w_oihw, uint16_t* w_split,
-                                       float* w_inv_scale, hkp_stream_t stream) {
-    HKP_CHECK_ARG(k > 0 && c >= 1 && c <= 4 && w_oihw && w_split && w_inv_scale, "hkp_stem_weight_pack_x3: bad args");
-    hipLaunchKernelGGL(stem_weight_pack_x3_kernel, dim3(k), dim3(256), 0, as_stream(stream), c, w_oihw,
-                       (_Float16*)w_split, w_inv_scale);
-    HKP_LAUNCH_CHECK("hkp_stem_weight_pack_x3");
     return HKP_OK;
 }
 

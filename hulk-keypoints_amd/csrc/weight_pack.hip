@@ -1,5 +1,6 @@
 // Batched f16x3 weight packing: every conv weight of a network packed in two
-// launches per optimizer step (the f16x3 conv operands of conv_x3.hip).
+// launches per optimizer step (the f16x3 conv operands of conv_x3.hip; one weight per
+// launch: pack_x3.hip).
 //
 // One training step changes every parameter, so every conv needs its forward
 // operand (hkp_weight_pack_x3: per output channel k) and, for the stride-1
@@ -47,7 +48,7 @@ struct PackTable {
     int n;
 };
 
-__device__ __forceinline__ float pk_scale(float m) {   // = conv_x3.hip pow2_scale_of
+__device__ __forceinline__ float pk_scale(float m) {   // = pack_x3.hip pow2_scale_of
     if (!(m > 0.f) || !(m < INFINITY)) return 1.f;
     int e;
     frexpf(m, &e);
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void weight_pack_b_kernel(const PackTable t) {
     }
 }
 
-// taps of output phase ph of a stride-2 conv along an axis of R taps (conv_x3.hip)
+// taps of output phase ph of a stride-2 conv along an axis of R taps (phase_taps, x3_plan.h)
 static int pk_phase_taps(int R, int pad, int ph, int* r_max) {
     for (int r = R - 1; r >= 0; --r)
         if ((((ph + pad - r) % 2) + 2) % 2 == 0) {

@@ -1,5 +1,5 @@
-// How an f16x3 / plain-fp16 conv is launched (conv_x3.hip), decided on the host: the
-// body, the tile height and width, stream-K or not, the split-K tail, the mixed-height
+// How an f16x3 / plain-fp16 conv is launched (conv_x3.hip; wg_x3_plan: wgrad_x3.hip),
+// decided on the host: the body, the tile height and width, stream-K or not, the split-K tail, the mixed-height
 // regions, the grids and the BN-partial tile sizes, as one plan (x3_launch_plan) that
 // the launcher, the kernel-name query and the BN-partial layout queries all read.
 // Plain C++17: nothing here asks a GPU runtime for anything — the CU count and the A/B

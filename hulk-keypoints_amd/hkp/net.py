@@ -255,7 +255,7 @@ def conv_bn(conv, bn, x, pol=None, layout="nhwc"):
 
 def _conv_fwd(conv, bn, x, pol, layout="nhwc", sk=True):
     """The conv of conv_bn → (y, BN tile partials or None); sk=False: no stream-K.
-    f16x3 and f16 run on the LDS-DMA MFMA kernels (conv_x3.hip); shapes those do
+    f16x3 and f16 run on the LDS-DMA MFMA kernels (conv_x3.hip and its x3_*.h); shapes those do
     not take (Cout % 64, or Cin % 64 for f16) run the exact fp32 MFMA kernel, which
     needs the fp32 activation."""
     passes = pol.passes

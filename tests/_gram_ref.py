@@ -1,5 +1,5 @@
 """Plain references of the Gram BN path (csrc/gram.hip and the fused BN-apply
-epilogue of csrc/conv_x3.hip) — shared by test_gram_ref_cpu.py and
+epilogue of csrc/conv_x3.hip and csrc/x3_duo.h) — shared by test_gram_ref_cpu.py and
 test_gpu_gram_edges.py.  numpy / torch only; nothing here imports hkp.
 
 The path is exact on small integers: fp16 holds them, their products are exact,

@@ -1,5 +1,6 @@
 """Plain fp64 references, hand-built operand planes, packing helpers, error bounds and case
-tables of the f16x3 / plain-fp16 convs (csrc/conv_x3.hip) — shared by test_x3_ref_cpu.py and
+tables of the f16x3 / plain-fp16 convs (csrc/conv_x3.hip, csrc/wgrad_x3.hip) — shared by
+test_x3_ref_cpu.py and
 test_gpu_x3_exact.py.  Helpers only; torch on the CPU, hkp only inside desc() / plans().
 
 The kernels take their operands PRE-SPLIT as two independent fp16 planes (hi, lo) and add

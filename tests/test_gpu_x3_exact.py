@@ -1,4 +1,5 @@
-"""The f16x3 / plain-fp16 convs (csrc/conv_x3.hip) at every kernel form, exact on integer
+"""The f16x3 / plain-fp16 convs (csrc/conv_x3.hip and its x3_*.h bodies, csrc/wgrad_x3.hip, the
+packers of csrc/pack_x3.hip) at every kernel form, exact on integer
 planes: hand-built UNRELATED hi / lo planes of small integers make every product and every
 partial sum an integer below 2^24 whatever the body, so the output must equal the fp64
 reference of exactly the products the mode keeps BIT FOR BIT (tests/_x3_ref.py has the

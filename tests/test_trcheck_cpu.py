@@ -1,7 +1,8 @@
 """tools/trcheck.py: the register hazard of untracked asm LDS reads (the compiler
 treats an inline-asm ds_read_b64_tr_b16 as complete when issued).  A synthetic
-listing pins the checker; the conv_x3 / gram kernels, cross-compiled for gfx950
-here, must have no access to a register whose asm read is still in flight."""
+listing pins the checker; the f16x3 conv (conv_x3, wgrad_x3, pack_x3) and gram
+kernels, cross-compiled for gfx950 here, must have no access to a register whose
+asm read is still in flight."""
 import os
 import re
 import shutil
@@ -49,7 +50,7 @@ def test_checker_finds_each_hazard(tmp_path, capsys):
 
 
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None, reason="hipcc absent")
-@pytest.mark.parametrize("src", ["conv_x3.hip", "gram.hip"])
+@pytest.mark.parametrize("src", ["conv_x3.hip", "wgrad_x3.hip", "pack_x3.hip", "gram.hip"])
 def test_kernels_have_no_inflight_register_access(tmp_path, src, capsys):
     out = tmp_path / "k.s"
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",

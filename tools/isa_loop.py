@@ -5,7 +5,11 @@ M<n> (n MFMAs), R / W (ds_read / ds_write), DMA (global_load_lds), LD (other
 global loads), v (VALU), [waitcnt], BARRIER.  Shows where the compiler put its
 waits and how the DMA pieces and LDS reads interleave with the MFMAs.
 
-    python tools/isa_loop.py "conv_x3_a3_kernel<3>" [--src csrc/conv_x3.hip]
+    python tools/isa_loop.py "conv_x3_a3_kernel<3>" [--src FILE]
+    python tools/isa_loop.py "wgrad_x3_kernel<256>"
+
+--src defaults to csrc/wgrad_x3.hip for a wgrad_x3* kernel and to csrc/conv_x3.hip (which
+includes the halo, stem and DUO bodies) otherwise.
 """
 import argparse
 import os
@@ -18,17 +22,22 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def mangled(name):
-    """conv_x3_a3_kernel<3> -> _ZN3hkp17conv_x3_a3_kernelILi3EEEvNS_6X3ArgsE (int args only)."""
+    """conv_x3_a3_kernel<3> -> _ZN3hkp17conv_x3_a3_kernelILi3EEEvNS_6X3ArgsE (int args only;
+    a wgrad_x3* kernel takes WgX3Args)."""
     m = re.match(r"(\w+)<([\d,\s]*)>", name)
     base, args = m.group(1), [a.strip() for a in m.group(2).split(",") if a.strip()]
-    return "_ZN3hkp%d%sI%sEEvNS_6X3ArgsE" % (len(base), base, "".join("Li%sE" % a for a in args))
+    block = "8WgX3Args" if base.startswith("wgrad_x3") else "6X3Args"
+    return "_ZN3hkp%d%sI%sEEvNS_%sE" % (len(base), base, "".join("Li%sE" % a for a in args), block)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("kernel")
-    ap.add_argument("--src", default=os.path.join(REPO, "hulk-keypoints_amd", "csrc", "conv_x3.hip"))
+    ap.add_argument("--src", default=None)
     args = ap.parse_args()
+    if args.src is None:
+        args.src = os.path.join(REPO, "hulk-keypoints_amd", "csrc",
+                                "wgrad_x3.hip" if args.kernel.startswith("wgrad_x3") else "conv_x3.hip")
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Per-kernel resource usage (VGPRs, spills, LDS, occupancy) of one .hip file: tools/kres.sh csrc/conv_x3.hip
+# Per-kernel resource usage (VGPRs, spills, LDS, occupancy) of one .hip file: tools/kres.sh csrc/conv_x3.hip (or wgrad_x3.hip, pack_x3.hip, ...)
 f=${1:?hip file}
 cd /tmp && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wno-unused-function \
     -Wno-unused-variable -c "$f" -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '

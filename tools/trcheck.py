@@ -8,8 +8,8 @@ graph from a gfx950 assembly listing (hipcc --cuda-device-only -S) with the
 in-flight reads as an ordered list (lgkmcnt(k) keeps the newest k; joins take
 the element-wise union) and prints every such access.
 
-    hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S csrc/conv_x3.hip -o /tmp/cx3.s
-    python tools/trcheck.py /tmp/cx3.s _ZN3hkp20wgrad_x3_halo_kernelENS_8WgX3ArgsE
+    hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S csrc/wgrad_x3.hip -o /tmp/wg3.s
+    python tools/trcheck.py /tmp/wg3.s _ZN3hkp20wgrad_x3_halo_kernelENS_8WgX3ArgsE
 """
 import re
 import sys
