@@ -47,7 +47,10 @@ checkpoint), and, through hkp_heat_loss_planes and with point labels only: LOSS_
 also hold "class_weights" (K floats, a weight per keypoint class: its planes' loss and gradient
 are scaled by it, a weight of 0 takes the class out of the loss) and "topk" (an int in 1..K:
 hard keypoint mining, per image only that many classes with the largest weighted loss are
-trained), and CLASS_LOSS (False; True: fit() prints `train class loss:` and `test class
+trained), and "lines" ("dense", the default: a Trainer step with line labels writes the dense
+target and runs the dense loss; "walk": it makes one hkp_heat_loss_lines call, the target in
+registers, and every loss choice of the point labels holds for line planes too; train.py's own
+loops read no line labels and pass the key over), and CLASS_LOSS (False; True: fit() prints `train class loss:` and `test class
 loss:` lines with the mean loss per pixel of each class, summed on the GPU and read once per
 epoch), and SYNTH (None: train.py reads data/<dataset>/ as the reference does; a dict such as
 {"train": 512, "test": 128, "seed": 0, "classes": ("cap", "tail", "crossing", "blob"),

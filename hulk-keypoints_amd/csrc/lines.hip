@@ -21,23 +21,13 @@
 // The survivors are evaluated by the definition, in slot order: the bits of the unculled
 // minimum.  A bound that is NaN keeps its segment.
 #include "common.h"
+#include "lines_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace hkp {
 
-constexpr int LINE_TW = 32, LINE_TH = 32;   // the tile: 8 threads x 4 pixels across, 32 rows
-constexpr float CULL_MARGIN = 2.f;          // pixels
-
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-// the definition's squared distance from (fx, fy) to the segment (x0, y0) + t (dx, dy)
-__device__ __forceinline__ float seg_d2(float fx, float fy, float x0, float y0, float dx, float dy, float inv) {
-    const float px = fx - x0, py = fy - y0;
-    const float t = fminf(fmaxf((px * dx + py * dy) * inv, 0.f), 1.f);
-    const float cx = px - t * dx, cy = py - t * dy;
-    return cx * cx + cy * cy;
-}
 
 // HAS_T / HAS_D: which outputs are written.  vec_t: target's base is 16-byte aligned and W
 // is even (two doubles a store); vec_d: d2's base is 16-byte aligned and W % 4 == 0 (four

@@ -24,6 +24,9 @@
 //                    plane), then the planes entry's launches with the mask flag set: a
 //                    masked pixel is selected out of the sum and of dheat, a plane's mean
 //                    and the elements divisor run over the kept pixels.
+//  * hkp_heat_loss_lines     the planes / masked entries over line labels [n][k][s][5]: the
+//                    same pre-, count- and finish-kernels around line_loss_walk_kernel,
+//                    which walks a plane's 32 x 32 tiles with lines.hip's staging and cull.
 //
 // All three losses are one body, heat_loss_walk_kernel, a template over (kind, 16-byte
 // path, mode); the mode says which planes take part and what a block leaves behind:
@@ -41,6 +44,7 @@
 #include <string>
 
 #include "common.h"
+#include "lines_dev.h"
 #include "loss_elem.h"
 
 #pragma clang fp contract(off)
@@ -133,7 +137,9 @@ __device__ __forceinline__ double masked_divisor(int norm_mode, long long kept, 
 // of its class that mask_count_kernel counted (cnt [n][mchunks][8], added here: integers,
 // any order); a plane without a kept pixel is not eligible, and HKP_NORM_ELEMENTS divides
 // by the eligible planes' kept pixels.
-template <bool MASKED>
+// RS, FO: the floats of a label record and where its flag is: (u, v, flag) for points,
+// (x0, y0, x1, y1, flag) for hkp_heat_loss_lines' segments.
+template <bool MASKED, int RS = 3, int FO = 2>
 __global__ __launch_bounds__(256) void planes_count_kernel(int planes, int m, double hw, int ignore, int norm_mode,
                                                           const float* __restrict__ pts,
                                                           const float* __restrict__ weights, int* __restrict__ info,
@@ -145,9 +151,9 @@ __global__ __launch_bounds__(256) void planes_count_kernel(int planes, int m, do
     int c = 0, np = 0;
     long long ne = 0;
     for (int p = threadIdx.x; p < planes; p += 256) {
-        const float* rec = pts + (long)p * 3 * m;
+        const float* rec = pts + (long)p * RS * m;
         int on = 0;
-        for (int j = 0; j < m; ++j) on += rec[3 * j + 2] > 0.f ? 1 : 0;
+        for (int j = 0; j < m; ++j) on += rec[RS * j + FO] > 0.f ? 1 : 0;
         bool el = !(ignore && on == 0);
         if (weights != nullptr && !(weights[p] > 0.f)) el = false;
         if constexpr (MASKED) {
@@ -484,6 +490,202 @@ __global__ __launch_bounds__(256) void planes_finish_kernel(int planes, int k, i
     }
 }
 
+// blocks per plane for a plane of `tiles` 32 x 32 tiles: multi_chunks' rule on tiles (one
+// tile a trip)
+static inline int line_chunks(int tiles) {
+    if (tiles <= MULTI_CHUNKS) return tiles;
+    const int trips = (tiles + MULTI_CHUNKS - 1) / MULTI_CHUNKS;
+    return (tiles + trips - 1) / trips;
+}
+
+// hkp_heat_loss_lines' walk: the PL_ modes of heat_loss_walk_kernel over line labels.  A
+// block owns one chunk of one plane (block = plane * chunks + chunk) and walks the plane's
+// LINE_TW x LINE_TH tiles chunk, chunk + chunks, ...; a thread has 4 pixels of a row in each.
+// The plane's records are read once per block, one slot per thread (waves 0 and 1); per
+// tile they are bounded, culled and compacted into LDS exactly as line_target_kernel does
+// it (lines.hip's header and DESIGN "Line labels" have the argument), so d2 and the target
+// have hkp_line_target's bits.  VEC4: W % 4 == 0 and 16-byte aligned heat and dheat: the 4
+// pixels are one load and one store; mword: W % 4 == 0 and a 4-byte aligned mask: the 4
+// mask bytes are one load.  Every thread adds its elements into one accumulator over all
+// its tiles; the block leaves one partial.
+template <int EK, bool VEC4, int MODE, bool MASKED>
+__global__ __launch_bounds__(256) void line_loss_walk_kernel(int s, int H, int W, int tiles_x, int tiles, int chunks,
+                                                            float den, float betaf, int mword,
+                                                            const double* __restrict__ inv_n_dev,
+                                                            const float* __restrict__ p,
+                                                            const float* __restrict__ lines,
+                                                            float* __restrict__ dheat, double* __restrict__ part,
+                                                            const int* __restrict__ info,
+                                                            const int* __restrict__ used,
+                                                            const float* __restrict__ weights,
+                                                            const uint8_t* __restrict__ mask, int k) {
+    static_assert(MODE == PL_ALL || MODE == PL_SUMS || MODE == PL_GRAD, "the planes modes");
+    __shared__ f32x4 sseg[HKP_LINE_MAX_S];
+    __shared__ float sinv[HKP_LINE_MAX_S];
+    __shared__ int swc[2];
+    __shared__ float swub[2];
+    __shared__ double red[4];
+    const long plane = blockIdx.x / chunks;
+    const int chunk = blockIdx.x - (int)plane * chunks;
+    const int HW = H * W;
+    const float* pp = p + plane * (long)HW;
+    float* dp = (MODE != PL_SUMS && dheat) ? dheat + plane * (long)HW : nullptr;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int tx = (threadIdx.x & 7) * 4, ty = threadIdx.x >> 3;
+    const int takes = __builtin_amdgcn_readfirstlane(MODE == PL_SUMS ? (info[plane] & 1) : used[plane]);
+    if (__builtin_expect(!takes, 0)) {   // the plane leaves the loss: dheat +0 over this block's tiles
+        if (dp) {
+            for (int tile = chunk; tile < tiles; tile += chunks) {
+                const int tile_y = tile / tiles_x;
+                const int x = (tile - tile_y * tiles_x) * LINE_TW + tx, y = tile_y * LINE_TH + ty;
+                if (y < H && x < W) {
+                    float* o = dp + (long)y * W + x;
+                    if constexpr (VEC4) {
+                        *(f32x4*)o = f32x4{0.f, 0.f, 0.f, 0.f};
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (x + e < W) o[e] = 0.f;
+                    }
+                }
+            }
+        }
+        return;
+    }
+    // ---- the plane's present slots and their constants, once (waves 0 and 1: slot = thread)
+    float x0 = 0.f, y0 = 0.f, dx = 0.f, dy = 0.f, inv = 0.f;
+    bool present = false;
+    if (threadIdx.x < s) {
+        const float* rec = lines + (plane * s + threadIdx.x) * 5;
+        present = rec[4] > 0.f;
+        if (present) {
+            x0 = rec[0], y0 = rec[1];
+            dx = rec[2] - x0, dy = rec[3] - y0;
+            const float l2 = dx * dx + dy * dy;
+            inv = l2 > 0.f ? 1.0f / l2 : 0.f;
+        }
+    }
+    const double inv_n = MODE == PL_SUMS ? 0.0 : inv_n_dev[0];
+    const double wd = weights ? (double)weights[plane] : 1.0;
+    const double beta = (double)betaf, bm1 = beta - 1.0;
+    const uint8_t* mi = nullptr;
+    int cbit = 0;
+    if constexpr (MASKED) {
+        const long img = plane / k;
+        cbit = (int)(plane - img * k);
+        mi = mask + img * (long)HW;
+    }
+    double acc = 0.0;
+    for (int tile = chunk; tile < tiles; tile += chunks) {   // block-uniform
+        const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+        const int xa = tile_x * LINE_TW, ya = tile_y * LINE_TH;
+        const int xb = min(xa + LINE_TW, W) - 1, yb = min(ya + LINE_TH, H) - 1;   // the tile's last pixel
+        const float fxa = (float)xa, fya = (float)ya, fxb = (float)xb, fyb = (float)yb;
+        const float mx = 0.5f * (fxa + fxb), my = 0.5f * (fya + fyb);
+        const float ex = fxb - fxa, ey = fyb - fya;
+        const float rad = 0.5f * sqrtf(ex * ex + ey * ey);
+        // ---- the bounds of every present segment over this tile
+        float lb = 0.f, ub = INFINITY;
+        bool on = present;
+        if (threadIdx.x < HKP_LINE_MAX_S) {
+            if (on) {
+                const float c = fmaxf(fmaxf(seg_d2(fxa, fya, x0, y0, dx, dy, inv), seg_d2(fxb, fya, x0, y0, dx, dy, inv)),
+                                      fmaxf(seg_d2(fxa, fyb, x0, y0, dx, dy, inv), seg_d2(fxb, fyb, x0, y0, dx, dy, inv)));
+                ub = sqrtf(c);
+                lb = sqrtf(seg_d2(mx, my, x0, y0, dx, dy, inv)) - rad;
+            }
+            float wub = ub;   // +inf where the slot is empty; fminf passes over a NaN
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) wub = fminf(wub, __shfl_xor(wub, o));
+            if (lane == 0) swub[wid] = wub;
+        }
+        __syncthreads();
+        // ---- drop what cannot be nearest anywhere in the tile; compact the rest
+        unsigned long long bal = 0;
+        if (threadIdx.x < HKP_LINE_MAX_S) {
+            const float best = fminf(swub[0], swub[1]);
+            on = on && !(lb > best + CULL_MARGIN);
+            bal = __ballot(on);
+            if (lane == 0) swc[wid] = __popcll(bal);
+        }
+        __syncthreads();
+        if (threadIdx.x < HKP_LINE_MAX_S && on) {
+            const int pos = (wid == 1 ? swc[0] : 0) + __popcll(bal & ((1ull << lane) - 1ull));
+            sseg[pos] = f32x4{x0, y0, dx, dy};
+            sinv[pos] = inv;
+        }
+        __syncthreads();
+        const int cnt = __builtin_amdgcn_readfirstlane(swc[0] + swc[1]);
+
+        // ---- 4 pixels of a row per thread, the survivors in slot order
+        const int x = xa + tx, y = ya + ty;
+        if (y < H && x < W) {
+            float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+            const float fy = (float)y;
+            for (int j = 0; j < cnt; ++j) {
+                const f32x4 sg = sseg[j];
+                const float iv = sinv[j];
+                const float py = fy - sg[1];
+                const float pydy = py * sg[3];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float px = (float)(x + e) - sg[0];
+                    const float t = fminf(fmaxf((px * sg[2] + pydy) * iv, 0.f), 1.f);
+                    const float cx = px - t * sg[2], cy = py - t * sg[3];
+                    d[e] = fminf(d[e], cx * cx + cy * cy);
+                }
+            }
+            const long at = (long)y * W + x;
+            float hv[4] = {0.5f, 0.5f, 0.5f, 0.5f};   // a pixel past the row's end is selected out below
+            if constexpr (VEC4) {
+                const f32x4 xv = *(const f32x4*)(pp + at);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) hv[e] = xv[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (x + e < W) hv[e] = pp[at + e];
+            }
+            uint32_t mw = 0;
+            if constexpr (MASKED) {
+                if (mword) {
+                    mw = *(const uint32_t*)(mi + at);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (x + e < W) mw |= (uint32_t)mi[at + e] << (8 * e);
+                }
+                mw >>= cbit;
+            }
+            float gv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = cnt > 0 ? expf(-d[e] / den) : 0.f;
+                double g;
+                const double l = loss_elem<EK>((double)hv[e], (double)t, inv_n, beta, bm1, &g);
+                const bool keep = (VEC4 || x + e < W) && !(MASKED && ((mw >> (8 * e)) & 1u));
+                if constexpr (MODE != PL_GRAD) acc += keep ? l : 0.0;
+                gv[e] = keep ? (float)(g * wd) : 0.f;
+            }
+            if (dp) {
+                float* o = dp + at;
+                if constexpr (VEC4) {
+                    *(f32x4*)o = f32x4{gv[0], gv[1], gv[2], gv[3]};
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (x + e < W) o[e] = gv[e];
+                }
+            }
+        }
+        __syncthreads();   // the next tile restages sseg / swc
+    }
+    if constexpr (MODE != PL_GRAD) {
+        const double sum = block_sum_d(acc, red);
+        if (threadIdx.x == 0) part[blockIdx.x] = sum;
+    }
+}
+
 static inline bool multi_sizes_ok(int32_t n, int32_t k, int32_t m, int32_t H, int32_t W) {
     // a plane is indexed with 32-bit integers, the block index too
     return n > 0 && k > 0 && m >= 1 && m <= MULTI_MAX_M && H > 0 && W > 0 && (long)H * W <= (1L << 30) &&
@@ -735,6 +937,113 @@ extern "C" int hkp_heat_loss_masked(int32_t n, int32_t k, int32_t m, int32_t H, 
     if (topk > 0 && dheat != nullptr) {
         launch_walk(lp, PL_GRAD, lp.inv_dev, st);
         HKP_LAUNCH_CHECK("hkp_heat_loss_masked(dheat)");
+    }
+    return HKP_OK;
+}
+
+// the masked entry's workspace, whatever mask is given: the planes entry's, then npix per
+// plane and the count pass's partial counts
+extern "C" int64_t hkp_heat_loss_lines_workspace(int32_t n, int32_t k, int32_t H, int32_t W) {
+    return hkp_heat_loss_masked_workspace(n, k, H, W);
+}
+
+extern "C" int hkp_heat_loss_lines(int32_t n, int32_t k, int32_t s, int32_t H, int32_t W, int32_t loss_kind,
+                                   int32_t absent_mode, int32_t norm_mode, float beta, int32_t topk, const float* heat,
+                                   const float* lines, const float* weights, const uint8_t* mask, float sigma,
+                                   double* loss, float* dheat, double* plane_loss, int32_t* plane_used,
+                                   int32_t* plane_pixels, void* workspace, hkp_stream_t stream) {
+    const char* who = "hkp_heat_loss_lines";
+    HKP_CHECK_ARG(n >= 1 && k >= 1 && H >= 1 && W >= 1 && (long)H * W <= (1L << 30) &&
+                      (long)n * k * MULTI_CHUNKS <= (1L << 30),
+                  "%s: bad sizes (n, k, H, W >= 1, H*W <= 2^30)", who);
+    HKP_CHECK_ARG(s >= 1 && s <= HKP_LINE_MAX_S, "%s: s = %d outside 1..%d", who, s, HKP_LINE_MAX_S);
+    HKP_CHECK_ARG(sigma > 0.f && sigma < INFINITY, "%s: sigma must be finite and > 0", who);
+    HKP_CHECK_ARG(heat && lines && loss && workspace, "%s: null tensor", who);
+    HKP_CHECK_ARG(loss_kind == HKP_LOSS_BCE || loss_kind == HKP_LOSS_MSE || loss_kind == HKP_LOSS_QFL,
+                  "%s: bad loss kind", who);
+    HKP_CHECK_ARG(absent_mode == HKP_ABSENT_ZERO || absent_mode == HKP_ABSENT_IGNORE, "%s: bad absent mode", who);
+    HKP_CHECK_ARG(norm_mode == HKP_NORM_ELEMENTS || norm_mode == HKP_NORM_INSTANCES, "%s: bad norm mode", who);
+    // NaN fails both comparisons
+    HKP_CHECK_ARG(loss_kind != HKP_LOSS_QFL || (beta >= 1.f && beta <= 8.f), "%s: beta %g outside [1, 8]", who,
+                  (double)beta);
+    HKP_CHECK_ARG(topk >= 0 && topk <= k && (topk == 0 || k <= 64),
+                  "%s: topk %d outside 0..k (k = %d; at most 64 classes with top-k)", who, topk, k);
+    HKP_CHECK_ARG(mask == nullptr || k <= MASK_MAX_K, "%s: k = %d classes, a mask byte holds %d", who, k, MASK_MAX_K);
+    const int planes = n * k, HW = H * W;
+    const int tiles_x = cdiv(W, LINE_TW), tiles = tiles_x * cdiv(H, LINE_TH);
+    const int chunks = line_chunks(tiles), nblocks = planes * chunks;
+    const bool vec4 = W % 4 == 0 && ((uintptr_t)heat & 15) == 0 && ((uintptr_t)dheat & 15) == 0;
+    const int mword = mask && W % 4 == 0 && ((uintptr_t)mask & 3) == 0;
+    const int ek = loss_kind == HKP_LOSS_BCE ? EK_BCE : loss_kind == HKP_LOSS_MSE ? EK_MSE : beta == 2.f ? EK_QFL2 : EK_QFLG;
+    const int ignore = absent_mode == HKP_ABSENT_IGNORE ? 1 : 0;
+    const float den = (float)(2.0 * (double)sigma * (double)sigma);
+    const double hw = (double)HW;
+    // the masked entry's layout: inv, the partials, S; info, used; npix, the mask counts
+    double* inv_dev = (double*)workspace;
+    double* part = inv_dev + 1;
+    double* S = part + (long)planes * MULTI_CHUNKS;
+    int* info = (int*)(S + planes);
+    int* used = info + planes;
+    int* npix = (int*)((char*)workspace + hkp_heat_loss_planes_workspace(n, k, H, W));
+    int* cnt = npix + planes;
+    hipStream_t st = as_stream(stream);
+    if (mask) {
+        const int mchunks = multi_chunks(((long)HW + 3) / 4);
+        if (HW % 4 == 0 && ((uintptr_t)mask & 3) == 0)
+            hipLaunchKernelGGL(mask_count_kernel<true>, dim3((unsigned)(n * mchunks)), dim3(256), 0, st, HW, mchunks,
+                               mask, cnt);
+        else
+            hipLaunchKernelGGL(mask_count_kernel<false>, dim3((unsigned)(n * mchunks)), dim3(256), 0, st, HW, mchunks,
+                               mask, cnt);
+        HKP_LAUNCH_CHECK("hkp_heat_loss_lines(count)");
+        hipLaunchKernelGGL((planes_count_kernel<true, 5, 4>), dim3(1), dim3(256), 0, st, planes, s, hw, ignore, norm_mode,
+                           lines, weights, info, used, inv_dev, k, mchunks, cnt, npix);
+    } else {
+        hipLaunchKernelGGL((planes_count_kernel<false, 5, 4>), dim3(1), dim3(256), 0, st, planes, s, hw, ignore, norm_mode,
+                           lines, weights, info, used, inv_dev, 0, 0, nullptr, nullptr);
+    }
+    HKP_LAUNCH_CHECK("hkp_heat_loss_lines(prepare)");
+    // the one (kind x 16-byte path x mode x masked) dispatch of the line walk
+    auto walk = [&](int mode) {
+#define HKP_LWALK(EK, V4, MD, MK)                                                                                   \
+    hipLaunchKernelGGL((line_loss_walk_kernel<EK, V4, MD, MK>), dim3((unsigned)nblocks), dim3(256), 0, st, s, H, W,  \
+                       tiles_x, tiles, chunks, den, beta, mword, inv_dev, heat, lines, dheat, part, info, used,      \
+                       weights, mask, k)
+#define HKP_LWALK_M(EK, V4, MD)            \
+    if (mask) HKP_LWALK(EK, V4, MD, true); \
+    else HKP_LWALK(EK, V4, MD, false)
+#define HKP_LWALK_V(EK, MD) \
+    if (vec4) { HKP_LWALK_M(EK, true, MD); } else { HKP_LWALK_M(EK, false, MD); }
+#define HKP_LWALK_K(MD)                                \
+    switch (ek) {                                      \
+        case EK_BCE: HKP_LWALK_V(EK_BCE, MD); break;   \
+        case EK_MSE: HKP_LWALK_V(EK_MSE, MD); break;   \
+        case EK_QFL2: HKP_LWALK_V(EK_QFL2, MD); break; \
+        default: HKP_LWALK_V(EK_QFLG, MD); break;      \
+    }
+        switch (mode) {
+            case PL_ALL: HKP_LWALK_K(PL_ALL) break;
+            case PL_SUMS: HKP_LWALK_K(PL_SUMS) break;
+            default: HKP_LWALK_K(PL_GRAD) break;
+        }
+#undef HKP_LWALK_K
+#undef HKP_LWALK_V
+#undef HKP_LWALK_M
+#undef HKP_LWALK
+    };
+    walk(topk == 0 ? PL_ALL : PL_SUMS);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_lines");
+    if (mask)
+        hipLaunchKernelGGL(planes_finish_kernel<true>, dim3(1), dim3(256), 0, st, planes, k, chunks, topk, hw, norm_mode,
+                           weights, info, used, part, S, inv_dev, loss, plane_loss, plane_used, npix, plane_pixels);
+    else
+        hipLaunchKernelGGL(planes_finish_kernel<false>, dim3(1), dim3(256), 0, st, planes, k, chunks, topk, hw,
+                           norm_mode, weights, info, used, part, S, inv_dev, loss, plane_loss, plane_used, nullptr,
+                           nullptr);
+    HKP_LAUNCH_CHECK("hkp_heat_loss_lines(finish)");
+    if (topk > 0 && dheat != nullptr) {
+        walk(PL_GRAD);
+        HKP_LAUNCH_CHECK("hkp_heat_loss_lines(dheat)");
     }
     return HKP_OK;
 }

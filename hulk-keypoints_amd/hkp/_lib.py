@@ -306,6 +306,10 @@ SIGNATURES = {
                                        _P, _I64, _P, _P, _P, _P]),
     # line labels lines [n,k,s,5] (x0, y0, x1, y1, flag): target f64 and / or d2 f32, each nullable
     "hkp_line_target": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    # the plane loss against line labels (lines in place of pts; weights and mask nullable)
+    "hkp_heat_loss_lines_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "hkp_heat_loss_lines": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _P,
+                                           _F, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 # the A/B instruments of the tools-only build (include/hulkkp_ab.h, `make ab`);

@@ -183,6 +183,69 @@ def heatmap_loss(heat, target=None, uv=None, sigma=8.0, kind="bce", pts=None, ab
     return _HeatLossFn.apply(heat, target, uv, sigma, kind, beta, norm)
 
 
+class _HeatLossLinesFn(torch.autograd.Function):
+    """ops.heat_loss_lines; the per-plane values leave as non-differentiable outputs
+    (plane_pixels is None without a mask)."""
+
+    @staticmethod
+    def forward(ctx, heat, lines, sigma, kind, absent, beta, norm, weights, topk, mask):
+        loss, dheat, plane_loss, plane_used, plane_pixels = ops.heat_loss_lines(
+            heat.contiguous(), lines, sigma, kind, absent, want_grad=torch.is_grad_enabled() or heat.requires_grad,
+            beta=beta, norm=norm, weights=weights, topk=topk, mask=mask)
+        ctx.save_for_backward(dheat)
+        if plane_pixels is None:
+            ctx.mark_non_differentiable(plane_loss, plane_used)
+        else:
+            ctx.mark_non_differentiable(plane_loss, plane_used, plane_pixels)
+        return loss, plane_loss, plane_used, plane_pixels
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gu, _gp):
+        (dheat,) = ctx.saved_tensors
+        return (dheat * g.to(dheat.dtype),) + (None,) * 9
+
+
+def line_heatmap_loss(heat, lines, sigma=8.0, kind="bce", absent="zero", *, pts=None, beta=2.0, norm="elements",
+                      weights=None, topk=None, mask=None, return_planes=False):
+    """The heatmap loss against line labels without the dense target (ops.heat_loss_lines):
+    ``lines`` float32 [N,K,S,5] (hkp.lines), and with ``pts`` [N,K,M,3] the labels are
+    lines.concat(lines.from_points(pts), lines), the points as zero-length segments.
+    Every choice of the point losses holds: ``kind`` "bce" / "mse" / "qfl" with ``beta``,
+    ``absent``, ``norm`` ("instances" counts present segment slots, points and pieces
+    alike), ``weights`` float32 [N,K], ``topk`` and ``mask`` uint8 [N,H,W] (K <= 8).  The
+    result is a 0-dim fp64 tensor; with ``return_planes`` it is (loss, plane_loss [N,K] f64,
+    plane_used [N,K] int32), and with a mask a fourth value, plane_pixels [N,K] int32, the
+    extras detached.  heatmap_loss(lines=) keeps its dense route and its limits."""
+    from . import lines as L
+    ops._loss_choice("line_heatmap_loss", kind, norm, beta)
+    if absent not in ops.ABSENT_MODES:
+        raise ops.HkpError("line_heatmap_loss: unknown absent %r (known: %s)" % (absent, ", ".join(ops.ABSENT_MODES)))
+    ops._planes_choice("line_heatmap_loss", weights, topk, heat)
+    ops._mask_choice("line_heatmap_loss", mask, heat)
+    if not isinstance(heat, torch.Tensor) or heat.dim() != 4:
+        raise ops.HkpError("line_heatmap_loss: heat must be a tensor [N,K,H,W]")
+    ops._lines_shape(lines, "line_heatmap_loss.lines")
+    if tuple(lines.shape[:2]) != tuple(heat.shape[:2]):
+        raise ops.HkpError("line_heatmap_loss: lines %s do not go with heat %s"
+                           % (tuple(lines.shape), tuple(heat.shape)))
+    if pts is not None:
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 4 or pts.shape[3] != 3 \
+                or tuple(pts.shape[:2]) != tuple(heat.shape[:2]):
+            raise ops.HkpError("line_heatmap_loss: pts must be [N,K,M,3] with heat's N and K, got %s"
+                               % (tuple(pts.shape) if isinstance(pts, torch.Tensor) else type(pts).__name__,))
+        if pts.shape[2] + lines.shape[2] > L.HKP_LINE_MAX_S:
+            raise ops.HkpError("line_heatmap_loss: %d points and %d segments a plane, at most %d slots together"
+                               % (pts.shape[2], lines.shape[2], L.HKP_LINE_MAX_S))
+    ops._need_lines(lines, "line_heatmap_loss.lines")
+    if pts is not None:
+        ops._need_pts(pts, "line_heatmap_loss.pts")
+        lines = L.concat(L.from_points(pts), lines)
+    out = _HeatLossLinesFn.apply(heat, lines, sigma, kind, absent, beta, norm, weights, topk, mask)
+    if not return_planes:
+        return out[0]
+    return out if mask is not None else out[:3]
+
+
 class HeatmapBCELoss(torch.nn.Module):
     """Drop-in for ``nn.BCELoss()(pred.double(), gt)`` (train.py:25) on GPU heatmaps."""
 

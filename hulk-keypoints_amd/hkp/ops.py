@@ -1889,6 +1889,58 @@ def heat_loss_masked(heat, pts, mask, sigma=8.0, kind="bce", absent="zero", want
     return loss, dheat, plane_loss, plane_used, plane_pixels
 
 
+def heat_loss_lines(heat, lines, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements",
+                    weights=None, topk=None, mask=None):
+    """heat_loss_planes / heat_loss_masked against line labels, the target of line_target
+    recomputed in registers, one entry (hkp_heat_loss_lines) → (loss 0-dim f64, dheat f32 or
+    None, plane_loss f64 [N,K], plane_used int32 [N,K], plane_pixels int32 [N,K] or None
+    without a mask); nothing is synchronised and no dense target is stored.
+    lines float32 [N,K,S,5] (x0, y0, x1, y1, flag; flag > 0: present), 1 <= S <= 128, on
+    heat's device: per pixel t = exp(-d2 / (2 sigma^2)) to the nearest present segment, 0 for
+    a plane with none; a point is a zero-length segment (hkp.lines.from_points).
+    kind, beta, absent, norm, weights, topk and mask mean what they mean in heat_loss_planes
+    and heat_loss_masked, with one reading: the present slots that norm="instances" counts are
+    segment slots, so a polyline of 12 pieces counts 12."""
+    import math
+    from ._lib import (HKP_ABSENT_IGNORE, HKP_ABSENT_ZERO, HKP_LOSS_BCE, HKP_LOSS_MSE, HKP_LOSS_QFL,
+                       HKP_NORM_ELEMENTS, HKP_NORM_INSTANCES, lib)
+    who = "heat_loss_lines"
+    beta = _loss_choice(who, kind, norm, beta)
+    if absent not in ABSENT_MODES:
+        raise HkpError("%s: unknown absent %r (known: %s)" % (who, absent, ", ".join(ABSENT_MODES)))
+    try:
+        sg = float(sigma)
+    except (TypeError, ValueError):
+        raise HkpError("%s: sigma must be a number, got %r" % (who, sigma))
+    if not (sg > 0 and math.isfinite(sg)):
+        raise HkpError("%s: sigma %s must be finite and > 0" % (who, sigma))
+    topk = _planes_choice(who, weights, topk, heat)
+    _mask_choice(who, mask, heat)
+    _lines_shape(lines, who + ".lines")
+    if isinstance(heat, torch.Tensor) and heat.dim() == 4:
+        if tuple(lines.shape[:2]) != tuple(heat.shape[:2]) or lines.device != heat.device:
+            raise HkpError("%s: lines %s on %s does not go with heat %s on %s"
+                           % (who, tuple(lines.shape), lines.device, tuple(heat.shape), heat.device))
+        if heat.numel() == 0 or heat.shape[2] * heat.shape[3] > 1 << 30:
+            raise HkpError("%s: bad heat size %s (no empty axis, H*W <= 2^30)" % (who, tuple(heat.shape)))
+    _need(heat, torch.float32, who + ".heat", 4)
+    _need_lines(lines, who + ".lines")
+    n, k, H, W = heat.shape
+    ws = torch.empty(lib().hkp_heat_loss_lines_workspace(n, k, H, W) // 8, device=heat.device, dtype=torch.float64)
+    loss = torch.empty((), device=heat.device, dtype=torch.float64)
+    dheat = torch.empty_like(heat) if want_grad else None
+    plane_loss = torch.empty((n, k), device=heat.device, dtype=torch.float64)
+    plane_used = torch.empty((n, k), device=heat.device, dtype=torch.int32)
+    plane_pixels = torch.empty((n, k), device=heat.device, dtype=torch.int32) if mask is not None else None
+    kd = {"bce": HKP_LOSS_BCE, "mse": HKP_LOSS_MSE, "qfl": HKP_LOSS_QFL}[kind]
+    call("hkp_heat_loss_lines", n, k, lines.shape[2], H, W, kd,
+         HKP_ABSENT_ZERO if absent == "zero" else HKP_ABSENT_IGNORE,
+         HKP_NORM_ELEMENTS if norm == "elements" else HKP_NORM_INSTANCES, beta, topk, _ptr(heat), _ptr(lines),
+         _ptr(weights), _ptr(mask), sg, _ptr(loss), _ptr(dheat), _ptr(plane_loss), _ptr(plane_used),
+         _ptr(plane_pixels), _ptr(ws), _stream())
+    return loss, dheat, plane_loss, plane_used, plane_pixels
+
+
 def heat_loss_multi(heat, pts, sigma=8.0, kind="bce", absent="zero", want_grad=True, *, beta=2.0, norm="elements",
                     weights=None, topk=None, mask=None):
     """heat_loss against the multi-instance target of pts float32 [N,K,M,3] (u, v,

@@ -126,6 +126,9 @@ def broadcast_state(model, src=0, group=None):
             off += t.numel()
 
 
+LINES_ROUTES = ("dense", "walk")      # loss_params["lines"]: how line labels reach the loss
+
+
 class Trainer:
     """One optimizer step per call, reference semantics (train.py:33-36)."""
 
@@ -200,8 +203,14 @@ class Trainer:
         self.params = list(model.parameters())
         self.loss_kind = loss
         self.loss_params = dict(loss_params or {})
-        if set(self.loss_params) - {"beta", "norm", "class_weights", "topk"}:
-            raise ValueError("loss_params may hold beta, norm, class_weights and topk, got %r" % (loss_params,))
+        if set(self.loss_params) - {"beta", "norm", "class_weights", "topk", "lines"}:
+            raise ValueError("loss_params may hold beta, norm, class_weights, topk and lines, got %r" % (loss_params,))
+        # how a step with line labels reaches the loss: "dense" (ops.line_target, then the
+        # dense ops.heat_loss) or "walk" (ops.heat_loss_lines, the target in registers)
+        self.lines_route = self.loss_params.pop("lines", "dense")
+        if self.lines_route not in LINES_ROUTES:
+            raise ValueError("loss_params['lines'] must be one of %s, got %r"
+                             % (", ".join(LINES_ROUTES), self.lines_route))
         self.topk = self.loss_params.pop("topk", None)
         ops._planes_choice("Trainer", None, self.topk)
         cw = self.loss_params.pop("class_weights", None)
@@ -285,6 +294,28 @@ class Trainer:
         ops._need_pts(pts, who + ".pts")
         return L.concat(L.from_points(pts), lines)
 
+    def _lines_walk_choice(self, x, uv, target, pts, lines, weights, mask):
+        """The checks of a step with line labels under loss_params["lines"] = "walk", before
+        the forward; returns the labels ops.heat_loss_lines gets: lines, with the points of
+        pts in front as zero-length segments."""
+        from . import lines as L
+        who = "Trainer"
+        if uv is not None or target is not None:
+            raise ops.HkpError("%s: pass lines alone or with pts, not with uv or target" % who)
+        ops._planes_choice(who, weights, self.topk)
+        ops._mask_choice(who, mask)
+        nk = (x.shape[0], self.model.num_keypoints)
+        if mask is not None and nk[1] > 8:
+            raise ops.HkpError("%s: a mask holds 8 class bits, the model has K = %d classes" % (who, nk[1]))
+        ops._lines_shape(lines, who + ".lines")
+        if tuple(lines.shape[:2]) != nk:
+            raise ops.HkpError("%s: lines %s do not go with %d images of %d classes" % ((who, tuple(lines.shape)) + nk))
+        ops._need_lines(lines, who + ".lines")
+        if pts is None:
+            return lines
+        ops._need_pts(pts, who + ".pts")
+        return L.concat(L.from_points(pts), lines)
+
     def forward_backward(self, x, uv=None, target=None, global_batch=None, pts=None, weights=None, gid=None,
                          mask=None, lines=None):
         """Labels: uv [B,K,2], a dense target [B,K,H,W] (fp64), or pts [B,K,M,3] (u, v,
@@ -293,6 +324,10 @@ class Trainer:
         is ops.line_target of the segments, the points of pts among them as zero-length
         segments, and the loss is the dense ops.heat_loss against it.  "bce" / "mse" and
         absent="zero" only; no weights, class_weights, topk or mask; tags read pts alone.
+        Under Trainer(loss_params={"lines": "walk"}) the same labels go to ops.heat_loss_lines
+        in one call, without a dense target, and every choice of the point path holds: "qfl"
+        with beta, norm, absent="ignore", class_weights, topk, weights and mask, with
+        plane_loss / plane_used / plane_pixels filled as there.
         weights: float32 [B,K] per-image plane weights (point labels only; see __init__).
         gid: int32 [B,K,M], Trainer(tags=...) only: the group of every slot of pts.
         global_batch (SyncBN): the job's batch size — the same on every rank, x
@@ -303,7 +338,8 @@ class Trainer:
         m = self.model
         planes = weights is not None or self._class_weights is not None or self.topk is not None or mask is not None
         self.plane_loss = self.plane_used = self.plane_pixels = None
-        if planes:                             # checked before the forward
+        walk = lines is not None and self.lines_route == "walk"
+        if planes and not walk:                # checked before the forward
             if target is not None or (pts is None) == (uv is None):
                 raise ops.HkpError("Trainer: class_weights, topk, weights and mask need pts or uv labels alone; a "
                                    "dense target is not supported")
@@ -318,11 +354,21 @@ class Trainer:
                 raise ops.HkpError("Trainer: gid goes with Trainer(tags=...)")
         elif pts is None or uv is not None or target is not None:      # checked before the forward
             raise ops.HkpError("Trainer: tags need pts labels alone; uv and a dense target carry no groups")
-        lab_lines = None if lines is None else self._lines_choice(x, uv, target, pts, lines, planes)
+        if walk:
+            lab_lines = self._lines_walk_choice(x, uv, target, pts, lines, weights, mask)
+        else:
+            lab_lines = None if lines is None else self._lines_choice(x, uv, target, pts, lines, planes)
         trace = net.Trace(self.policy)
         kw = {} if self.tags is None else {"tags": True}           # tags off: the call as it always was
         hm, _, low = net.keypoints_forward(m.resnet.net, x, m.num_keypoints, heat=True, trace=trace, **kw)
-        if lab_lines is not None:
+        if walk:
+            w = self._plane_weights(weights, hm.device)
+            if w is not None:
+                w = w.expand(hm.shape[0], hm.shape[1]).contiguous()
+            loss, dheat, self.plane_loss, self.plane_used, self.plane_pixels = ops.heat_loss_lines(
+                hm, lab_lines, self.sigma, self.loss_kind, self.absent, want_grad=True, weights=w, topk=self.topk,
+                mask=mask, **self.loss_params)
+        elif lab_lines is not None:
             tgt, _ = ops.line_target(lab_lines, hm.shape[2], hm.shape[3], self.sigma)
             loss, dheat = ops.heat_loss(hm, tgt, None, self.sigma, self.loss_kind, want_grad=True)
         elif planes:

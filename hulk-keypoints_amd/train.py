@@ -102,9 +102,10 @@ def forward(sample_batched, model):
 def _planes_kw(pred_gauss):
     """LOSS_PARAMS' class_weights as heatmap_loss's weights [B,K] (the other keys pass as they
     are), and return_planes with CLASS_LOSS; the parameters unchanged when neither is set."""
-    if "class_weights" not in LOSS_PARAMS and not CLASS_LOSS:
+    if "class_weights" not in LOSS_PARAMS and "lines" not in LOSS_PARAMS and not CLASS_LOSS:
         return LOSS_PARAMS
-    kw = {k: v for k, v in LOSS_PARAMS.items() if k != "class_weights"}
+    # "lines" is hkp.train.Trainer's route for line labels; these loops read point labels
+    kw = {k: v for k, v in LOSS_PARAMS.items() if k not in ("class_weights", "lines")}
     if "class_weights" in LOSS_PARAMS:
         dev = pred_gauss.device
         key = (dev, tuple(float(v) for v in LOSS_PARAMS["class_weights"]))

@@ -1421,6 +1421,50 @@ int hkp_peaks_group(int32_t n, int32_t k, int32_t p, int32_t h, int32_t w, int32
 int hkp_line_target(int32_t n, int32_t k, int32_t s, int32_t H, int32_t W, float sigma,
                     const float* lines, double* target, float* d2, hkp_stream_t stream);
 
+/* The plane loss against line labels, the target recomputed in registers: the contract
+ * of hkp_heat_loss_masked (and, without a mask, of hkp_heat_loss_planes) with lines
+ * [n][k][s][5] in place of pts; not in the reference, and the entries above are
+ * unchanged.  Two definitions above are composed and nothing is added to either:
+ * target:    per pixel t is the fp32 value hkp_line_target defines, with its flag rule, its
+ *            operation order, den = (float)(2.0 * (double)sigma * (double)sigma), d2 over the
+ *            present slots in slot order, t = expf(-d2 / den), +0.0f for a plane without a
+ *            present slot; no contraction.  An empty slot is never read into a result, a
+ *            point is a zero-length segment.  The dense target is never stored.
+ * element:   loss and gradient are hkp_heat_loss_planes' per-element formulas on
+ *            ((double)heat, (double)t) under the divisor D; dheat = (float)(g * (double)w).
+ *            With a mask, a masked pixel is selected out of the sum and gets dheat +0.0f.
+ * rules:     eligibility, S, plane_loss (S / (H*W), or S / n_bc with a mask; -1.0 where not
+ *            eligible), plane_used, plane_pixels, the topk ranking with its tie and NaN
+ *            rules, D and the loss are those of hkp_heat_loss_planes (mask == NULL) and of
+ *            hkp_heat_loss_masked (mask given), word for word, with one reading:
+ * P:         "present slots" are present SEGMENT slots: a plane's P is the number of its
+ *            slots with flag > 0, points and pieces alike, so a polyline of 12 pieces counts
+ *            12 under HKP_NORM_INSTANCES.
+ * S[b][c]:   a block owns one chunk of a plane's 32 x 32 tiles (chunk, chunk + chunks, ...);
+ *            every thread adds its elements into one fp64 accumulator over all its tiles,
+ *            the block's sum is one partial, and S is the partials in chunk order.  The
+ *            order differs from the other entries': S agrees with theirs to rounding, dheat
+ *            (which depends on S only through topk) bit for bit where the targets do.
+ * A plane that takes no part gets dheat +0.0f; its heat, its mask and its records beyond
+ * the flags are never read.  Per tile the kernel drops the segments that cannot be nearest
+ * to any of its pixels, as hkp_line_target does: the outputs are the bits of the definition.
+ * launches:  the mask's count pass (with a mask), a pre-kernel, the pass, the one-block
+ *            finish and, with topk > 0 and dheat, the second pass.  No atomics on floating
+ *            values, no host synchronisation: the same input gives the same bits.
+ * weights, mask, dheat, plane_loss, plane_used and plane_pixels are nullable; plane_pixels
+ * is written only when a mask is given.  n, k, H, W >= 1, H*W <= 2^30, 1 <= s <=
+ * HKP_LINE_MAX_S, sigma finite and > 0, heat, lines, loss and workspace non-null, the
+ * kind / absent / norm codes of hkp_heat_loss_planes, beta in [1, 8] for HKP_LOSS_QFL (NaN
+ * refused), 0 <= topk <= k and k <= 64 when topk > 0, k <= 8 with a mask; anything else is
+ * HKP_ERR_BAD_ARG and nothing is launched or written.
+ * workspace: hkp_heat_loss_lines_workspace(n, k, H, W) bytes. */
+int64_t hkp_heat_loss_lines_workspace(int32_t n, int32_t k, int32_t H, int32_t W);
+int hkp_heat_loss_lines(int32_t n, int32_t k, int32_t s, int32_t H, int32_t W, int32_t loss_kind,
+                        int32_t absent_mode, int32_t norm_mode, float beta, int32_t topk, const float* heat,
+                        const float* lines, const float* weights, const uint8_t* mask, float sigma, double* loss,
+                        float* dheat, double* plane_loss, int32_t* plane_used, int32_t* plane_pixels,
+                        void* workspace, hkp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

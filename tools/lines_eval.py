@@ -10,7 +10,11 @@ Evaluated on `--held-out` fixed scenes of seed + 1: the four point classes with
 hkp.metrics.KeypointMetrics exactly as synth_train does (peaks of the low-res logits,
 max_peaks = instances, radius 1, threshold 0.1), and the cable plane with
 hkp.lines.LineMetrics (radius 4 px, threshold 0.5) on the full-size heatmap.  One JSON line
-per run, appended to --log; one run each: a record, not a gate."""
+per run, appended to --log; one run each: a record, not a gate.
+
+--lines walk trains the cable plane through hkp_heat_loss_lines (Trainer(loss_params={"lines":
+"walk"})) instead of the dense target; with it --loss qfl --beta 2 is possible.  --cable-only
+skips the runs without the cable plane."""
 import argparse
 import json
 import os
@@ -41,7 +45,10 @@ def run(backbone, with_cable, args, dev):
     model = KeypointsGauss(K, hw[0], hw[1], backbone=backbone, pretrained=False)
     model.load_state_dict(recipe.seeded_state_dict(backbone, 23))
     model = model.to(dev)
-    tr = train.Trainer(model, lr=args.lr, loss="bce", absent="zero")
+    params = {"lines": args.lines} if with_cable else {}
+    if args.loss == "qfl":
+        params["beta"] = args.beta
+    tr = train.Trainer(model, lr=args.lr, loss=args.loss, absent="zero", loss_params=params)
     losses = []
     torch.cuda.synchronize()
     t0 = time.time()
@@ -64,7 +71,8 @@ def run(backbone, with_cable, args, dev):
                 lm.update(hm, batch[2])
     res = metrics.compute()
     out = {"backbone": backbone, "classes": list(classes), "steps": args.steps, "batch": B, "lr": args.lr,
-           "train_seconds": secs, "train_img_per_s": B * args.steps / secs,
+           "loss": args.loss, "beta": args.beta if args.loss == "qfl" else None,
+           "lines": args.lines if with_cable else None, "train_seconds": secs, "train_img_per_s": B * args.steps / secs,
            "final_train_loss": torch.stack([v.detach().double().reshape(()) for v in losses[-20:]]).mean().item(),
            "recall": {c: r["recall"] for c, r in zip(POINTS, res["per_class"])},
            "instances": {c: r["instances"] for c, r in zip(POINTS, res["per_class"])},
@@ -85,6 +93,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--backbones", default="resnet18,resnet34")
+    ap.add_argument("--loss", default="bce", choices=("bce", "mse", "qfl"))
+    ap.add_argument("--beta", type=float, default=2.0)
+    ap.add_argument("--lines", default="dense", choices=("dense", "walk"))
+    ap.add_argument("--cable-only", action="store_true")
     ap.add_argument("--log", default=os.path.join(REPO, "profiles", "lines_eval.log"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -93,7 +105,7 @@ def main():
     torch.cuda.set_device(dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
     for backbone in args.backbones.split(","):
-        for with_cable in (False, True):
+        for with_cable in ((True,) if args.cable_only else (False, True)):
             line = json.dumps(dict(tool="lines_eval", device=torch.cuda.get_device_name(0),
                                    **run(backbone, with_cable, args, dev)))
             print(line, flush=True)
